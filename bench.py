@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: candidate link-pairs scored per second on a synthetic ogbl-collab-shaped graph.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config collab] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config collab] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs: set-up, warm-up (and the untimed probes that pick the launch path and the
+attention form), ONE timed window of exactly K steps, the scores of its last step under DIR (``--dump-outputs``), the
+JSON line.  ``--full`` adds everything else the benchmark measures: five windows (median), the encoder timed alone, the
+bf16 mode, per-kernel timing and rooflines, the trained-weights leg and the CPU baseline.
 
 ``python bench.py --gpus N`` without torchrun's environment starts its own N ranks (child processes, one per GPU,
 before this process touches a GPU) and rank 0 prints the one JSON line with ``n_gpus: N``.
@@ -256,10 +261,17 @@ def main():
                     help="distinct candidate batches cycled through (resident in HBM before the timed region; a captured "
                          "graph copies the ids of the step's batch into its static input).  0 = one per stream: a "
                          "stream then always scores the same resident batch, read in place (round 3's default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (the legs switched by --weights, "
+                         "--no-cpu-baseline, --no-kernel-timing and --no-bf16, the encoder alone, rooflines) and time "
+                         "--repeats windows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores of the last timed step (rank 0: the [pairs_per_step] probabilities the "
+                         "timed path returns) as DIR/scores.npy, float32")
     ap.add_argument("--weights", default="both", choices=("random", "both"),
-                    help="both: after the headline (random-init weights, as the bench contract prescribes) the model is "
-                         "trained for --train-steps steps of the repo's own training step on the synthetic graph and "
-                         "the same timed window is run again (extra key `trained_weights`: flips per entry, the "
+                    help="(--full) both: after the headline (random-init weights, as the bench contract prescribes) "
+                         "the model is trained for --train-steps steps of the repo's own training step on the synthetic "
+                         "graph and the same timed window is run again (extra key `trained_weights`: flips per entry, the "
                          "attention kernel `auto` then picks, ms per step)")
     ap.add_argument("--train-steps", type=int, default=150)
     ap.add_argument("--train-lr", type=float, default=1e-3)
@@ -280,9 +292,9 @@ def main():
                          "fill the machine, and the fork / join events of a side stream cost more than the overlap "
                          "inside one step gives (collab-like, 6 streams: 0.199 ms/step with, 0.192 without)")
     ap.add_argument("--no-side-stream", action="store_true", help="= --side-stream off")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed windows of K steps each; `value` / `ms_per_step` are the MEDIAN window, min/median/max of "
-                         "all are reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed windows of K steps each (default 1, with --full 5); `value` / `ms_per_step` are the "
+                         "MEDIAN window, min/median/max of all are reported")
     ap.add_argument("--encoder", default="auto", choices=("auto", "replicated", "sharded", "gather_once"),
                     help="N > 1: every rank runs the whole encoder / rows sharded with an all-gather per layer / the last "
                          "layer and the per-node attention projections sharded with ONE all-gather of [X | Z]; "
@@ -314,6 +326,10 @@ def main():
                          "0.1355 / 0.135, 8 streams 0.142 / 0.136 / 0.135 (every kernel fills the chip by itself now: more "
                          "streams only lengthen the fill and drain of a window); 2: 0.144, 16: 0.145 at 20 steps")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:   # a plain run: the headline window only, none of the extra legs
+        args.weights, args.no_cpu_baseline, args.no_kernel_timing, args.no_bf16 = "random", True, True, True
 
     rank, world, local = LD.init_from_env()
     if world != args.gpus and rank == 0:
@@ -428,6 +444,9 @@ def main():
     #      would time Python, not the kernels)
     rows_probe = None
     planned_by_form = {}
+    # the probes time windows as long as the timed one, up to a bound: what a run costs besides its K timed steps must
+    # not grow with K
+    probe_steps = min(args.steps, 500)
     if os.environ.get("LPF_SELECT4_REGIONS"):                    # A/B aid: "0" = lpf_select3_plan / _run for the type-major consumers
         model.select4_regions = os.environ["LPF_SELECT4_REGIONS"] != "0"
     if os.environ.get("LPF_TAIL_SKIP_EMPTY"):                    # A/B aid: "0" = the plain rows tail
@@ -461,11 +480,11 @@ def main():
                 torch.cuda.synchronize()
                 barrier()
                 t0 = time.perf_counter()
-                for i in range(max(args.steps, 40)):
+                for i in range(max(probe_steps, 40)):
                     probe_step(i)
                 torch.cuda.synchronize()
                 barrier()
-                t = LD.max_over_ranks(time.perf_counter() - t0, dev) * 1e3 / max(args.steps, 40)
+                t = LD.max_over_ranks(time.perf_counter() - t0, dev) * 1e3 / max(probe_steps, 40)
                 rows_probe[mode] = min(t, rows_probe.get(mode, t))
         model.attention_rows = rows_probe["rows"] <= rows_probe["records"]
         rows_probe = {k: round(v, 4) for k, v in rows_probe.items()}
@@ -536,11 +555,11 @@ def main():
             torch.cuda.synchronize()
             barrier()
             t0 = time.perf_counter()
-            for i in range(args.steps):
+            for i in range(probe_steps):
                 step_on(i)
             torch.cuda.synchronize()
             barrier()
-            probe[mode] = LD.max_over_ranks(time.perf_counter() - t0, dev) * 1e3 / args.steps
+            probe[mode] = LD.max_over_ranks(time.perf_counter() - t0, dev) * 1e3 / probe_steps
         launch = min(probe, key=probe.get)
         launch_probe = {k: round(v, 4) for k, v in probe.items()}
 
@@ -577,49 +596,54 @@ def main():
     else:
         overflows = sum(0 if model.check_selection(lane) else 1 for lane in lanes)
     assert overflows == 0, "a timed step overflowed its selection workspace: the window is invalid"
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), out.float().cpu().numpy())
     rep_ms = [e * 1e3 / args.steps for e in rep_s]
     elapsed = float(np.median(rep_s))   # `value`: the median window
 
-    # ---- encoder, timed separately (same output: h stays valid)
-    barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    enc_reps = 5
-    for _ in range(enc_reps):
-        h2 = model.propagate()
-    torch.cuda.synchronize()
-    barrier()
-    encoder_ms = LD.max_over_ranks((time.perf_counter() - t0) * 1e3 / enc_reps, dev)
-    # ... and with what every NEW encoder output costs on top: the two per-node projections Z | Y of the attention
-    # (one [N, D] x [D, 2D] product, cached per encoder output; the gather_once layout computes them inside propagate())
-    barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(enc_reps):
-        h2 = model.propagate()
-        model._node_keys(h2, model._fold())
-        if model.query_from == "table":
-            model._node_y(h2, model._fold())
-    torch.cuda.synchronize()
-    barrier()
-    node_keys_ms = max(0.0, LD.max_over_ranks((time.perf_counter() - t0) * 1e3 / enc_reps, dev) - encoder_ms)
-    # the same with the gathered per-layer table stored in bf16 (lpf_gemm_f32_out_bf16 + lpf_spmm_csr_bf16)
-    encoder_bf16 = None
-    if not args.no_bf16:
-        model.encoder_precision = "bf16"
-        h16 = model.propagate()
+    # ---- encoder, timed separately (same output: h stays valid); --full
+    encoder_ms = node_keys_ms = encoder_bf16 = None
+    if args.full:
+        barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        enc_reps = 5
+        for _ in range(enc_reps):
+            h2 = model.propagate()
         torch.cuda.synchronize()
         barrier()
+        encoder_ms = LD.max_over_ranks((time.perf_counter() - t0) * 1e3 / enc_reps, dev)
+        # ... and with what every NEW encoder output costs on top: the two per-node projections Z | Y of the attention
+        # (one [N, D] x [D, 2D] product, cached per encoder output; the gather_once layout computes them inside
+        # propagate())
+        barrier()
+        torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(enc_reps):
-            h16 = model.propagate()
+            h2 = model.propagate()
+            model._node_keys(h2, model._fold())
+            if model.query_from == "table":
+                model._node_y(h2, model._fold())
         torch.cuda.synchronize()
         barrier()
-        encoder_bf16 = {"encoder_ms": round(LD.max_over_ranks((time.perf_counter() - t0) * 1e3 / enc_reps, dev), 4),
-                        "max_abs_diff_x_node_vs_f32": float((h16 - h).abs().max())}
-        model.encoder_precision = "f32"
-        del h16
-    del h2
+        node_keys_ms = max(0.0, LD.max_over_ranks((time.perf_counter() - t0) * 1e3 / enc_reps, dev) - encoder_ms)
+        # the same with the gathered per-layer table stored in bf16 (lpf_gemm_f32_out_bf16 + lpf_spmm_csr_bf16)
+        if not args.no_bf16:
+            model.encoder_precision = "bf16"
+            h16 = model.propagate()
+            torch.cuda.synchronize()
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(enc_reps):
+                h16 = model.propagate()
+            torch.cuda.synchronize()
+            barrier()
+            encoder_bf16 = {"encoder_ms": round(LD.max_over_ranks((time.perf_counter() - t0) * 1e3 / enc_reps, dev), 4),
+                            "max_abs_diff_x_node_vs_f32": float((h16 - h).abs().max())}
+            model.encoder_precision = "f32"
+            del h16
+        del h2
 
     # ---- bf16 throughput mode (extra keys; the headline stays fp32 = the reference's precision): same steps with
     #      model.precision = "bf16" (bf16 storage of Z + bf16 matrix cores in the attention kernel)
@@ -760,16 +784,19 @@ def main():
         del h_rand, saved
         h = model.propagate()
         torch.cuda.synchronize()
-    value_incl_encoder = world * bs / ((ms_per_step + encoder_ms + node_keys_ms) * 1e-3)
+    value_incl_encoder = (None if encoder_ms is None else
+                          world * bs / ((ms_per_step + encoder_ms + node_keys_ms) * 1e-3))
 
     kt = KernelTimer.summary() if not args.no_kernel_timing else {}
-    # one instrumented encoder pass for the aggregation kernel's roofline -- on EVERY rank: a row-sharded encoder
-    # all-gathers, and a collective issued by rank 0 alone would wait for ever
-    KernelTimer.reset()
-    KernelTimer.enabled = True
-    model.propagate()
-    enc = KernelTimer.summary()
-    KernelTimer.enabled = False
+    enc = {}
+    if args.full:
+        # one instrumented encoder pass for the aggregation kernel's roofline -- on EVERY rank: a row-sharded encoder
+        # all-gathers, and a collective issued by rank 0 alone would wait for ever
+        KernelTimer.reset()
+        KernelTimer.enabled = True
+        model.propagate()
+        enc = KernelTimer.summary()
+        KernelTimer.enabled = False
 
     result = None
     if rank == 0:
@@ -999,18 +1026,21 @@ def main():
                                         "replicated": "(every rank runs it, no exchange)"}[enc_plan["chosen"]])
                        if world > 1 else "single GPU",
                        "encoder_plan": enc_plan},
-            "encoder_ms": round(encoder_ms, 4), "node_keys_ms": round(node_keys_ms, 4),
-            "value_incl_encoder": round(value_incl_encoder, 1),
-            "ms_per_step_instrumented": None if instrumented_ms is None else round(instrumented_ms, 4),
             "ms_per_step_repeats": {"n": len(rep_ms), "min": round(min(rep_ms), 4),
                                     "median": round(float(np.median(rep_ms)), 4), "max": round(max(rep_ms), 4)},
-            "roofline": roofline, "cpu_baseline": cpu,
-            "pair_stage_hbm_frac": None if pair_stage is None else pair_stage["hbm_frac_of_8TBs"],
-            "pair_stage": pair_stage, "trained_weights": trained,
-            "bf16_mode": bf16, "kernels": kernels, "rooflines": rooflines,
             "setup_s": dict({k: round(v, 2) for k, v in setup.items()}, ppr_producer=args.ppr,
                             index_bytes=index_bytes),
         }
+        if args.full:
+            result.update({
+                "encoder_ms": round(encoder_ms, 4), "node_keys_ms": round(node_keys_ms, 4),
+                "value_incl_encoder": round(value_incl_encoder, 1),
+                "ms_per_step_instrumented": None if instrumented_ms is None else round(instrumented_ms, 4),
+                "roofline": roofline, "cpu_baseline": cpu,
+                "pair_stage_hbm_frac": None if pair_stage is None else pair_stage["hbm_frac_of_8TBs"],
+                "pair_stage": pair_stage, "trained_weights": trained,
+                "bf16_mode": bf16, "kernels": kernels, "rooflines": rooflines,
+            })
         print(json.dumps(result), flush=True)
     barrier()
     if world > 1:

@@ -75,7 +75,7 @@ def test_bench_dress_rehearsal_eight_ranks_on_one_gpu(encoder):
     timing and the one JSON line of rank 0 -- everything of an N = 8 run but the exchange over xGMI."""
     import json
     p, left = _bench(["--gpus", "8", "--config", "tiny", "--steps", "4", "--warmup", "2", "--repeats", "2", "--encoder",
-                      encoder, "--no-cpu-baseline", "--weights", "random", "--no-bf16", "--spinup", "0"])
+                      encoder, "--no-cpu-baseline", "--weights", "random", "--no-bf16", "--spinup", "0", "--full"])
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -91,7 +91,7 @@ def test_bench_capture_failure_on_one_rank_falls_back_everywhere():
     barriers and reductions, a rank on another path would wait for ever -- and the run still ends with one JSON line."""
     import json
     p, left = _bench(["--gpus", "4", "--config", "tiny", "--steps", "4", "--warmup", "2", "--repeats", "2",
-                      "--no-cpu-baseline", "--weights", "random", "--no-bf16", "--spinup", "0"],
+                      "--no-cpu-baseline", "--weights", "random", "--no-bf16", "--spinup", "0", "--full"],
                      {"LPF_BENCH_FAIL_CAPTURE_RANK": "2"})
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

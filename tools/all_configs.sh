@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 : > $OUT
 for c in ${2:-collab ddi cora ppa citation2}; do
   echo "== $c" >> $OUT
-  timeout 900 python3 bench.py --config $c --no-cpu-baseline --repeats 3 2>/dev/null | tail -1 > gpurun_out/${TAG}_line_$c.json
+  timeout 900 python3 bench.py --full --config $c --no-cpu-baseline --repeats 3 2>/dev/null | tail -1 > $(dirname $OUT)/${TAG}_line_$c.json
   python3 tools/all_configs_fmt.py < gpurun_out/${TAG}_line_$c.json >> $OUT 2>&1
 done
 python3 - <<PY

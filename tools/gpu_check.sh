@@ -10,5 +10,5 @@ echo "pytest rc=$?" >> gpurun_out/${TAG}_tests.log
 grep -E "passed|failed|FAILED|rc=|Error" gpurun_out/${TAG}_tests.log | tail -12
 for c in $CONFIGS; do
   echo "== $c"
-  timeout 900 python3 bench.py --config $c --no-cpu-baseline --repeats 3 2>/dev/null | tail -1 | python3 tools/all_configs_fmt.py
+  timeout 900 python3 bench.py --full --config $c --no-cpu-baseline --repeats 3 2>/dev/null | tail -1 | python3 tools/all_configs_fmt.py
 done

@@ -1,9 +1,9 @@
 #!/bin/bash
-# Same-lease A/B of pair_rows / tail build variants under the pipelined bench (driver form, no extra legs) + serial kernel
+# Same-lease A/B of pair_rows / tail build variants under the pipelined bench (driver form + kernel timing) + serial kernel
 # times.  Usage: tools/r06_ab.sh  (variants from $VARIANTS, one EXTRA string per line; "" = the default build)
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
-BARGS="--gpus 1 --steps 20 --warmup 5 --weights random --no-cpu-baseline --no-bf16 --rows on ${BENCH_ARGS:-}"
+BARGS="--full --gpus 1 --steps 20 --warmup 5 --weights random --no-cpu-baseline --no-bf16 --rows on ${BENCH_ARGS:-}"
 while IFS= read -r ex; do
   for f in ${TOUCH:-pair_rows tail_chain}; do touch lpformer_amd/csrc/$f.hip; done
   make -C lpformer_amd/csrc -j8 EXTRA="$ex" > gpurun_out/ab_build.log 2>&1 || { echo "[$ex] build failed"; tail -5 gpurun_out/ab_build.log; continue; }
