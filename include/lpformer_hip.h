@@ -34,7 +34,7 @@ extern "C" {
 #define LPF_ERR_LAUNCH (-3)      /* hipLaunch / runtime error (see lpf_last_hip_error)  */
 #define LPF_ERR_NO_DEVICE (-4)   /* no gfx950 device visible                            */
 
-#define LPF_ABI_VERSION 9
+#define LPF_ABI_VERSION 10
 
 /* GEMM / row-wise epilogue flags */
 #define LPF_FLAG_RELU 1u
@@ -697,6 +697,28 @@ int lpf_self_ppr(int64_t n, const int64_t *adj_rowptr, const int32_t *adj_col, c
  * src/models/link_transformer.py:229-237,290-291): lpformer_amd.LinkTransformer._patch_removed. */
 int lpf_csr_lookup_f32(int64_t nq, int64_t n, const int64_t *rows, const int64_t *cols, const int64_t *rowptr,
                        const int32_t *col, const float *val, float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Pair heuristics (pair_heuristics.hip): common neighbours, Adamic-Adar, Resource Allocation of candidate pairs on a
+ * binary CSR -- the typing adjacency.  Replaces compute_edge_cn (src/train/eval.py:21-41: (A[a] & A[b]).sum() over
+ * dense adj[edge].to_dense() rows per batch), which test_by_metric (eval.py:44-77) bins the test positives by, the
+ * analysis behind run.py's --bymetric / --percentile arguments (src/run.py:195-196, parsed and never read there).
+ * ---------------------------------------------------------------------------------------------- */
+/* Walked rows longer than this go to the workgroup-per-pair kernel (split_threshold < 0 selects it). */
+#define LPF_HEUR_SPLIT_DEFAULT 32
+/* For pair p = (a, b) = (pairs[p], pairs[pairs_ld + p]) of a CSR with sorted, unique columns (values ignored):
+ *   cn[p] = |N(a) & N(b)| (deg(a) when a == b; a stored self-loop counts like any other column),
+ *   aa[p] = sum over w in N(a) & N(b) of w_aa[w],  ra[p] = the same sum of w_ra[w]
+ * (w_aa[w] = 1 / ln deg(w), 0 where deg <= 1; w_ra[w] = 1 / deg(w): float[n] tables built once per graph).
+ * Ids outside [0, n) give 0 / 0 / 0.  cn / aa / ra may each be NULL (not computed); w_aa / w_ra may be NULL when aa /
+ * ra is.  A pair walks its shorter row (equal lengths: the row of min(a, b)) and binary-searches the other: pairs whose
+ * walked row holds at most split_threshold entries are flattened 64 probes per wavefront, longer ones get a 256-thread
+ * workgroup each (a second kernel over a list the first one fills).  Sums are fp64 in an order fixed by the pair
+ * alone, rounded to fp32 once: h(a, b) and h(b, a) are bitwise equal, and so are two runs.
+ * scratch: int32[P + 1] (the long-pair list).  P < 2^31 - 1. */
+int lpf_pair_heuristics_f32(int64_t P, int64_t n, const int64_t *pairs, int64_t pairs_ld, const int64_t *rowptr,
+                            const int32_t *col, const float *w_aa, const float *w_ra, int32_t split_threshold,
+                            int32_t *scratch, int32_t *cn, float *aa, float *ra, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training step of the pair stage (pair_train.hip): the forward of get_pos_encodings

@@ -166,3 +166,60 @@ def ranking_metrics(pos: torch.Tensor, neg: torch.Tensor) -> dict:
     rank = 0.5 * (optimistic + pessimistic).to(torch.float32) + 1.0
     return {"Hits@10": float((rank <= 10).float().mean().item()), "Hits@50": float((rank <= 50).float().mean().item()),
             "Hits@100": float((rank <= 100).float().mean().item()), "MRR": float((1.0 / rank).mean().item())}
+
+
+# Metrics by heuristic bin (src/train/eval.py:44-77 ``test_by_metric``, behind run.py's --bymetric / --percentile,
+# src/run.py:195-196).  The reference's function is unfinished: its predictions are ``...`` placeholders (eval.py:64,66),
+# and it overwrites its bin list with the per-edge counts (``cn_vals = compute_edge_cn(...)``, eval.py:68) before
+# looping over ``cn_vals`` as bins.  What follows is the intended logic: the bins of eval.py:62, half-open [lo, hi)
+# (eval.py:70), each bin's positives against ALL negatives with the OGB hits@K rule (eval.py:71-73).
+CN_BINS = ((0, 1), (1, 3), (3, 10), (10, 1_000_000))
+
+
+def metrics_by_bin(pos: torch.Tensor, neg: torch.Tensor, values: torch.Tensor, bins=CN_BINS,
+                   k_list=(20, 50, 100)) -> list:
+    """Ranking metrics of the positives split by a per-positive value (a pair heuristic: CN, AA, RA, PPR ...).
+
+    pos [P] scores of the positives, values [P] the value each is binned by, bins a sequence of half-open [lo, hi).
+    ``neg`` 1-D (the OGB Hits layout): every bin's positives against ALL negatives, ``Hits@K`` for K in ``k_list``
+    (``hits_at_k``).  ``neg`` [P, K] (HeaRT / citation2: each positive's own negatives): ``ranking_metrics`` over the
+    rows of the bin.  Returns one dict per bin: ``bin`` (lo, hi), ``count`` and the metrics -- NaN for an empty bin."""
+    pos = torch.as_tensor(pos).reshape(-1)
+    neg = torch.as_tensor(neg)
+    values = torch.as_tensor(values).reshape(-1).to(pos.device)
+    if values.numel() != pos.numel():
+        raise ValueError(f"values has {values.numel()} entries, pos {pos.numel()}")
+    per_row = neg.dim() == 2
+    if per_row and neg.shape[0] != pos.numel():
+        raise ValueError(f"neg [P, K] must have one row per positive ({pos.numel()}), got {tuple(neg.shape)}")
+    if neg.dim() > 2:
+        raise ValueError("neg must be 1-D (shared negatives) or [P, K] (per-positive negatives)")
+    neg = neg.to(pos.device)
+    keys = ("Hits@10", "Hits@50", "Hits@100", "MRR") if per_row else tuple(f"Hits@{k}" for k in k_list)
+    out = []
+    for lo, hi in bins:
+        m = (values >= lo) & (values < hi)
+        count = int(m.sum().item())
+        res = {"bin": (lo, hi), "count": count}
+        if count == 0:
+            res.update({k: float("nan") for k in keys})
+        elif per_row:
+            res.update(ranking_metrics(pos[m], neg[m]))
+        else:
+            res.update({f"Hits@{k}": hits_at_k(pos[m], neg, k) for k in k_list})
+        out.append(res)
+    return out
+
+
+def quantile_bins(values: torch.Tensor, qs=(0.25, 0.5, 0.75)) -> tuple:
+    """Bins for ``metrics_by_bin`` cut at quantiles of the positives' own values (the --percentile style of split,
+    run.py:196): edges e_i = quantile(values, q_i) (linear interpolation, torch.quantile), bins
+    (-inf, e_1), [e_1, e_2), ..., [e_k, inf).  Repeated edges give empty bins (NaN metrics), not merged ones."""
+    v = torch.as_tensor(values).reshape(-1).to(torch.float64)
+    if v.numel() == 0:
+        raise ValueError("quantile_bins needs at least one value")
+    q = torch.as_tensor(list(qs), dtype=torch.float64)
+    if q.numel() and (bool((q < 0).any()) or bool((q > 1).any()) or bool((q[1:] < q[:-1]).any())):
+        raise ValueError("qs must be ascending and lie in [0, 1]")
+    edges = [float("-inf")] + [float(e) for e in torch.quantile(v.cpu(), q)] + [float("inf")]
+    return tuple((edges[i], edges[i + 1]) for i in range(len(edges) - 1))
