@@ -147,9 +147,11 @@ def pack_wfold(wfold: np.ndarray) -> np.ndarray:
 
 
 def to_bf16_bits(x: np.ndarray) -> np.ndarray:
-    """fp32 -> bf16 bit patterns (uint16), round to nearest even."""
-    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+    """fp32 -> bf16 bit patterns (uint16), round to nearest even; NaN is quieted (high half | 0x40) as the kernels'
+    lpf_f32_to_bf16 does -- the rounding increment would carry a NaN's payload into an infinity or wrap it to zero."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+    r = (u + 0x7FFF + ((u >> 16) & 1)) >> 16
+    return np.where((u & 0x7FFFFFFF) > 0x7F800000, (u >> 16) | 0x40, r).astype(np.uint16)
 
 
 def pack_wfold_bf16(wfold: np.ndarray) -> np.ndarray:
