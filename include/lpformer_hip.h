@@ -34,7 +34,7 @@ extern "C" {
 #define LPF_ERR_LAUNCH (-3)      /* hipLaunch / runtime error (see lpf_last_hip_error)  */
 #define LPF_ERR_NO_DEVICE (-4)   /* no gfx950 device visible                            */
 
-#define LPF_ABI_VERSION 10
+#define LPF_ABI_VERSION 11
 
 /* GEMM / row-wise epilogue flags */
 #define LPF_FLAG_RELU 1u
@@ -719,6 +719,41 @@ int lpf_csr_lookup_f32(int64_t nq, int64_t n, const int64_t *rows, const int64_t
 int lpf_pair_heuristics_f32(int64_t P, int64_t n, const int64_t *pairs, int64_t pairs_ld, const int64_t *rowptr,
                             const int32_t *col, const float *w_aa, const float *w_ra, int32_t split_threshold,
                             int32_t *scratch, int32_t *cn, float *aa, float *ra, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Top-K link recommendation (recommend.hip): the candidate pairs of a batch of sources and the segmented top-K of
+ * their scores.  The reference only ranks a positive against negatives it is handed (src/train/testing.py:14-121).
+ * ---------------------------------------------------------------------------------------------- */
+/* Include rows longer than this go to the workgroup-per-source kernel (split_threshold < 0 selects it). */
+#define LPF_REC_SPLIT_DEFAULT 256
+/* Candidates of source u = sources[s]: the entries v of u's row of the include CSR (inc_*, fp32 values) whose value is
+ * > 0 and >= min_val -- or every v of [0, n) when inc_rowptr is NULL -- minus u's row of the exclusion CSR (exc_*,
+ * values ignored; NULL: none) and, with exclude_self, minus u; ascending v.  Sources outside [0, n) have none.
+ * Count pass: count[s] = the number of candidates.  Fill pass: offset[s] = the exclusive scan of the counts of this
+ * same call (P = their total); writes pairs[offset[s] + r] = u, pairs[P + offset[s] + r] = v_r (the [2, P] int64 layout
+ * of the scoring sweep).  Include rows of at most split_threshold entries take one wavefront per source (exclusion
+ * row staged in LDS when short, ranks by ballot); longer rows, and every row when inc_rowptr is NULL, get a 256-thread
+ * workgroup each from a second kernel over a list the first fills.  scratch: int32[S + 1].  S, n < 2^31. */
+int lpf_rec_candidate_count(int64_t S, int64_t n, const int64_t *sources, const int64_t *inc_rowptr,
+                            const int32_t *inc_col, const float *inc_val, float min_val, const int64_t *exc_rowptr,
+                            const int32_t *exc_col, int32_t exclude_self, int32_t split_threshold, int32_t *scratch,
+                            int64_t *count, void *stream);
+int lpf_rec_candidate_fill(int64_t S, int64_t n, const int64_t *sources, const int64_t *inc_rowptr,
+                           const int32_t *inc_col, const float *inc_val, float min_val, const int64_t *exc_rowptr,
+                           const int32_t *exc_col, int32_t exclude_self, int32_t split_threshold, int32_t *scratch,
+                           const int64_t *offset, int64_t P, int64_t *pairs, void *stream);
+/* Largest k of the segmented top-K. */
+#define LPF_TOPK_MAX_K 1024
+/* Segment s = positions [seg_ptr[s], seg_ptr[s + 1]) of score / cand (each shorter than 2^32 - 1).  Ranks a segment by
+ * the 64-bit key (order-preserving uint32 of the score, -0.0 -> +0.0, NaN below -inf) << 32 | ~(position in the
+ * segment), descending -- ties go to the earlier position -- and writes its first c = min(k, len) entries:
+ * ids[s * k + e] = cand[.], scores[s * k + e] = score[.] (bits as stored), e >= c padded with -1 / -inf; counts[s] = c.
+ * Segments of <= 256 entries: one wavefront each, a bitonic network in registers.  Longer ones: one 512-thread
+ * workgroup each (a second kernel over a list the first fills); <= 4096 entries are bitonic-sorted in LDS, longer ones
+ * first narrowed by an MSB-first radix select (256-bin LDS histogram per 8 bits) to <= 4096 keys.  Deterministic, no
+ * float atomics.  scratch: int32[S + 1].  1 <= k <= LPF_TOPK_MAX_K. */
+int lpf_segment_topk_f32(int64_t S, const int64_t *seg_ptr, const float *score, const int64_t *cand, int32_t k,
+                         int32_t *scratch, int64_t *ids, float *scores, int64_t *counts, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training step of the pair stage (pair_train.hip): the forward of get_pos_encodings

@@ -6,6 +6,7 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
     calc_ppr, calc_ppr_gpu, get_ppr     drop-ins for src/util/calc_ppr_scores.py (host OpenMP push / MI355X push)
     evaluate                            encoder-once, device-resident evaluation sweep + ranking metrics (also by bin)
     pair_heuristics                     CN / Adamic-Adar / Resource Allocation (+ PPR, feature cosine) of pairs
+    recommend                           top-K new links per source node (device candidates, scoring, top-K)
     graph, data                         CSR containers and the data-dict builder
 """
 from . import evaluate, graph, mask_delta, readers  # noqa: F401
@@ -15,7 +16,8 @@ from .graphed import GraphedScorer, PlannedScorer  # noqa: F401
 from .link_transformer import MLP, LinkTransformer, mlp_score  # noqa: F401
 from .ppr import calc_ppr, calc_ppr_gpu, get_ppr, load_or_calc_ppr, ppr_coo  # noqa: F401
 from .pyg_api import LPFormer  # noqa: F401
+from .recommend import Recommendations, recommend  # noqa: F401
 
 __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_ppr_gpu", "get_ppr",
            "load_or_calc_ppr", "ppr_coo", "graph", "evaluate", "GraphedScorer", "PlannedScorer", "RemovedEdges",
-           "pair_heuristics"]
+           "pair_heuristics", "recommend", "Recommendations"]

@@ -223,3 +223,50 @@ def quantile_bins(values: torch.Tensor, qs=(0.25, 0.5, 0.75)) -> tuple:
         raise ValueError("qs must be ascending and lie in [0, 1]")
     edges = [float("-inf")] + [float(e) for e in torch.quantile(v.cpu(), q)] + [float("inf")]
     return tuple((edges[i], edges[i + 1]) for i in range(len(edges) - 1))
+
+
+def recommendation_metrics(rec, sources, held_out, ks=(10, 20, 50, 100)) -> dict:
+    """Mean recall@k and hit-rate@k of top-K recommendations (``lpformer_amd.recommend``) against held-out links.
+
+    ``rec``: a ``Recommendations`` (or anything with ``ids`` int [S, K], best first, -1 padding); ``sources`` [S] the
+    source of each row; ``held_out`` [P, 2] directed edges (u, v), duplicates counted once.  For a row whose source has
+    T >= 1 held-out targets: recall@k = |top-k ids that are targets| / T (an id repeated in a row counts once),
+    hit@k = 1 if any of them is a target.  Both are averaged over those rows only; rows without targets are left out.
+    A k above K uses all K columns.  Returns ``{"recall@k": ..., "hit@k": ..., "n_sources": rows counted}`` (NaN
+    metrics when no row has a target).  Pure torch, on the device of ``rec.ids``."""
+    ids = torch.as_tensor(getattr(rec, "ids", rec))
+    dev = ids.device
+    ids = ids.to(torch.int64)
+    src = torch.as_tensor(sources).to(dev, torch.int64).reshape(-1)
+    ho = torch.as_tensor(held_out).to(dev, torch.int64)
+    if ids.dim() != 2 or ids.shape[0] != src.numel():
+        raise ValueError("rec.ids must be [S, K] with one row per source")
+    if ho.dim() != 2 or ho.shape[1] != 2:
+        raise ValueError("held_out must be [P, 2] directed edges")
+    S, K = ids.shape
+    parts = [src, ids.reshape(-1), ho.reshape(-1)]
+    N = int(max(int(t.max()) for t in parts if t.numel()) + 1) if any(t.numel() for t in parts) else 1
+    N = max(N, 1)
+    keys = torch.unique(ho[:, 0] * N + ho[:, 1]) if ho.numel() else torch.empty(0, dtype=torch.int64, device=dev)
+    n_t = torch.searchsorted(keys, src * N + N) - torch.searchsorted(keys, src * N)
+    # first occurrence of each id in its row: a stable sort puts repeats after the first
+    srt, order = torch.sort(ids, dim=1, stable=True)
+    first_sorted = torch.ones_like(srt, dtype=torch.bool)
+    first_sorted[:, 1:] = srt[:, 1:] != srt[:, :-1]
+    first = torch.empty_like(first_sorted).scatter_(1, order, first_sorted)
+    q = src[:, None] * N + ids.clamp_min(0)
+    pos = torch.searchsorted(keys, q.reshape(-1)).reshape(S, K).clamp_max(max(keys.numel() - 1, 0))
+    hit = (ids >= 0) & first & (keys.numel() > 0) & (keys[pos] == q if keys.numel() else torch.zeros_like(first))
+    rows = n_t > 0
+    n_rows = int(rows.sum())
+    out = {}
+    for k in ks:
+        kk = min(int(k), K)
+        h = hit[:, :kk].sum(dim=1).to(torch.float64)
+        if n_rows == 0:
+            out[f"recall@{k}"] = out[f"hit@{k}"] = float("nan")
+            continue
+        out[f"recall@{k}"] = float((h[rows] / n_t[rows].to(torch.float64)).mean())
+        out[f"hit@{k}"] = float((h[rows] > 0).to(torch.float64).mean())
+    out["n_sources"] = n_rows
+    return out

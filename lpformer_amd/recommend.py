@@ -1,0 +1,230 @@
+"""Top-K link recommendation: for each source node u, the K candidates v the model scores highest.
+
+The reference only ranks a positive against negatives it is handed (src/train/testing.py:14-121); answering "which K
+new links of u are most likely?" meant building the candidate pairs by hand, scoring them and writing a segmented
+top-K.  Here the three steps are one call:
+
+1. candidates on the device (``lpf_rec_candidate_count`` / ``lpf_rec_candidate_fill``, csrc/recommend.hip): u's PPR row
+   or every node, minus the exclusion row (by default the model's own typing adjacency) and u itself;
+2. scoring through ``evaluate.score_edges`` (logits) -- no scoring path of its own;
+3. ranking by ``lpf_segment_topk_f32``: by logit, ties to the earlier candidate (the smaller id for the generated
+   modes), -0.0 == +0.0, NaN below -inf.
+
+Sources are processed in chunks of whole sources whose candidate total stays within ``max_pairs``.  The candidates
+and the ranking of a source depend on that source and its candidates' logits alone, never on the chunking.  The
+logits themselves come from ``score_edges``, whose value for a pair can move by a few ulps with the batch the pair
+lands in (at most 9e-7 on the test fixtures), so the scores -- and, on such a near-tie, the order -- can too.
+"""
+from __future__ import annotations
+
+from typing import List, NamedTuple, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib, graph
+from ._lib import check, ptr
+
+MAX_K = 1024                 # LPF_TOPK_MAX_K (include/lpformer_hip.h)
+CANDIDATE_MODES = ("ppr", "all")
+
+
+class Recommendations(NamedTuple):
+    ids: torch.Tensor           # int64 [S, k]: candidate ids, best first; -1 past counts
+    scores: torch.Tensor        # float32 [S, k]: probabilities (logits with logits=True); -inf past counts
+    counts: torch.Tensor        # int64 [S]: min(k, n_candidates)
+    n_candidates: torch.Tensor  # int64 [S]: |C(u)|
+
+
+def plan_chunks(counts, max_pairs: int) -> List[Tuple[int, int]]:
+    """Split sources 0..S-1 with ``counts[s]`` candidates each into consecutive ranges [lo, hi) whose candidate total is
+    at most ``max_pairs``; a source with more than ``max_pairs`` candidates gets a range of its own (a segment is never
+    split).  Every source lies in exactly one range; no range is empty.  Pure host logic."""
+    if int(max_pairs) < 1:
+        raise ValueError("max_pairs must be positive")
+    c = np.asarray(counts, dtype=np.int64).reshape(-1)
+    if (c < 0).any():
+        raise ValueError("counts must be non-negative")
+    chunks, lo, acc = [], 0, 0
+    for s, v in enumerate(c.tolist()):
+        if s > lo and acc + v > max_pairs:
+            chunks.append((lo, s))
+            lo, acc = s, 0
+        acc += v
+    if c.size:
+        chunks.append((lo, int(c.size)))
+    return chunks
+
+
+def _check_args(sources, k, candidates):
+    """Argument checks that need no device.  Returns (sources as a 1-D int64 tensor, explicit candidates or None)."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"k must be an integer in [1, {MAX_K}]; got {k!r}")
+    src = torch.as_tensor(sources)
+    if src.dtype.is_floating_point or src.dtype.is_complex or src.dtype == torch.bool:
+        raise TypeError("sources must hold integer node ids")
+    if src.dim() != 1:
+        raise ValueError("sources must be a 1-D tensor [S]")
+    explicit = None
+    if isinstance(candidates, str):
+        if candidates not in CANDIDATE_MODES:
+            raise ValueError(f"candidates must be one of {CANDIDATE_MODES} or an int tensor [S, M]; got {candidates!r}")
+    else:
+        explicit = torch.as_tensor(candidates)
+        if explicit.dtype.is_floating_point or explicit.dtype.is_complex or explicit.dtype == torch.bool:
+            raise TypeError("explicit candidates must hold integer node ids")
+        if explicit.dim() != 2 or explicit.shape[0] != src.shape[0]:
+            raise ValueError("explicit candidates must be [S, M] with one row per source")
+    return src, explicit
+
+
+def _exclusion(model, exclude, test_set, dev):
+    if exclude is None:
+        return None
+    if isinstance(exclude, str):
+        if exclude != "adj":
+            raise ValueError("exclude must be 'adj', None, a graph.CSR or a graph.DeviceCSR")
+        with torch.cuda.device(dev):
+            return model._device_graph("mask", model._data_obj("mask", test_set))
+    if isinstance(exclude, graph.DeviceCSR):
+        if exclude.rowptr.device != dev:
+            raise ValueError("the exclusion DeviceCSR must live on the model's device")
+        g = exclude
+    elif isinstance(exclude, graph.CSR):
+        g = graph.CSR(exclude.rowptr, exclude.col, None, exclude.n).to_device(dev)
+    else:
+        raise TypeError("exclude must be 'adj', None, a graph.CSR or a graph.DeviceCSR")
+    if g.n != model.num_nodes:
+        raise ValueError(f"the exclusion graph has {g.n} nodes, the model {model.num_nodes}")
+    return g
+
+
+def _range_check(src: torch.Tensor, n: int, what: str):
+    if src.numel() and (int(src.min()) < 0 or int(src.max()) >= n):
+        bad = src[(src < 0) | (src >= n)][0]
+        raise IndexError(f"{what}: node id {int(bad)} outside [0, {n})")
+
+
+def _stream(dev):
+    return torch._C._cuda_getCurrentRawStream(dev.index)
+
+
+def generate_candidates(n: int, sources: torch.Tensor, include, min_ppr: float, exclude, exclude_self: bool,
+                        split_threshold: int = -1):
+    """The candidate counts of device int64 ``sources`` ([S] int64) and a function ``fill(lo, hi, total)`` that returns the
+    [2, P] int64 pairs of sources lo..hi-1 (ascending v per source).  ``include``: a DeviceCSR with fp32 values (the
+    PPR rows) or None (every node); ``exclude``: a DeviceCSR or None."""
+    dev = sources.device
+    S = sources.numel()
+    hip = _lib.hip()
+    inc = (ptr(include.rowptr), ptr(include.col), ptr(include.val)) if include is not None else (None, None, None)
+    exc = (ptr(exclude.rowptr), ptr(exclude.col)) if exclude is not None else (None, None)
+    counts = torch.zeros(S, dtype=torch.int64, device=dev)
+    scratch = torch.empty(S + 1, dtype=torch.int32, device=dev)
+    st = _stream(dev)
+    if S:
+        check(hip.lpf_rec_candidate_count(S, n, ptr(sources), *inc, float(min_ppr), *exc, int(bool(exclude_self)),
+                                          int(split_threshold), ptr(scratch), ptr(counts), st),
+              "lpf_rec_candidate_count")
+
+    def fill(lo: int, hi: int, total: int) -> torch.Tensor:
+        pairs = torch.empty((2, total), dtype=torch.int64, device=dev)
+        if total:
+            seg = counts[lo:hi]
+            offset = torch.cumsum(seg, 0) - seg
+            check(hip.lpf_rec_candidate_fill(hi - lo, n, sources.data_ptr() + lo * 8, *inc, float(min_ppr), *exc,
+                                             int(bool(exclude_self)), int(split_threshold), ptr(scratch), ptr(offset),
+                                             total, ptr(pairs), _stream(dev)), "lpf_rec_candidate_fill")
+        return pairs
+    return counts, fill
+
+
+def segment_topk(seg_ptr: torch.Tensor, score: torch.Tensor, cand: torch.Tensor, k: int):
+    """(ids int64 [S, k], scores float32 [S, k], counts int64 [S]) of the segments ``seg_ptr`` (int64 [S + 1]) of
+    ``score`` (float32) / ``cand`` (int64): the top min(k, len) of each segment by score, ties to the earlier position,
+    -0.0 == +0.0, NaN below -inf; padding -1 / -inf (``lpf_segment_topk_f32``)."""
+    if not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"k must be in [1, {MAX_K}]")
+    dev = score.device
+    S = seg_ptr.numel() - 1
+    ids = torch.empty((S, k), dtype=torch.int64, device=dev)
+    out = torch.empty((S, k), dtype=torch.float32, device=dev)
+    counts = torch.empty(S, dtype=torch.int64, device=dev)
+    if S > 0:
+        seg_ptr = seg_ptr.to(dev, torch.int64).contiguous()
+        score = score.to(torch.float32).contiguous()
+        cand = cand.to(dev, torch.int64).contiguous()
+        scratch = torch.empty(S + 1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            check(_lib.hip().lpf_segment_topk_f32(S, ptr(seg_ptr), ptr(score), ptr(cand), int(k), ptr(scratch),
+                                                  ptr(ids), ptr(out), ptr(counts), _stream(dev)),
+                  "lpf_segment_topk_f32")
+    return ids, out, counts
+
+
+@torch.no_grad()
+def recommend(model, score_func, sources, k: int = 100, *, candidates="ppr", min_ppr: float = 0.0, exclude="adj",
+              exclude_self: bool = True, test_set: bool = False, h=None, batch_size: int = 32768,
+              max_pairs: int = 1 << 24, logits: bool = False, split_threshold: int = -1) -> Recommendations:
+    """The ``k`` highest-scoring candidates v of every source u in ``sources`` (int [S], host or device; duplicates are
+    independent rows).
+
+    ``candidates``: ``"ppr"`` -- the entries of u's row of the split's PPR matrix (``data["ppr"]``, ``data["ppr_test"]``
+    with ``test_set``) whose fp32 value is > 0 and >= ``min_ppr``; ``"all"`` -- every node; or an int tensor [S, M] of
+    explicit candidates, taken as given (no exclusion, duplicates kept).  ``exclude``: ``"adj"`` (the model's typing
+    adjacency of the split), None, a ``graph.CSR`` or a ``graph.DeviceCSR``; ``exclude_self`` drops v = u.
+
+    Candidates are scored by ``evaluate.score_edges(..., logits=True)`` (``h`` propagated once when not given), ranked by
+    logit with ties to the earlier candidate (the smaller id for the generated modes).  ``scores`` are
+    ``torch.sigmoid`` of the logits, or the logits themselves with ``logits=True``.  Sources go in chunks of whole
+    sources of at most ``max_pairs`` candidates (one source may exceed it alone).  The counts are read back once to
+    size the chunks.  ``split_threshold``: PPR-row length above which a source's candidates are built by a whole
+    workgroup (negative: the library default)."""
+    from . import evaluate
+    src, explicit = _check_args(sources, k, candidates)
+    k = int(k)
+    if int(max_pairs) < 1 or int(batch_size) < 1:
+        raise ValueError("max_pairs and batch_size must be positive")
+    if model.training:
+        raise NotImplementedError("recommend needs model.eval(), as score_pairs does")
+    dev = model.device
+    if dev.type != "cuda":
+        raise _lib.LpfError("recommend: the model must live on an MI355X; lpformer_amd has no CPU fallback")
+    n = int(model.num_nodes)
+    _range_check(src, n, "recommend: sources")
+    S = src.numel()
+    with torch.cuda.device(dev):
+        src = src.to(dev, torch.int64).contiguous()
+        if explicit is not None:
+            cand = explicit.to(dev, torch.int64).contiguous()
+            _range_check(cand, n, "recommend: candidates")
+            M = cand.shape[1]
+            n_cand = torch.full((S,), M, dtype=torch.int64, device=dev)
+            counts_host = np.full(S, M, dtype=np.int64)
+
+            def fill(lo, hi, total):
+                return torch.stack([src[lo:hi].repeat_interleave(M), cand[lo:hi].reshape(-1)])
+        else:
+            include = None
+            if candidates == "ppr":
+                include = model._device_graph("ppr", model._data_obj("ppr", test_set))
+            exc = _exclusion(model, exclude, test_set, dev)
+            n_cand, fill = generate_candidates(n, src, include, min_ppr, exc, exclude_self, split_threshold)
+            counts_host = n_cand.cpu().numpy()       # the one read-back: it sizes the chunks and their outputs
+        if h is None:
+            h = model.propagate(test_set=test_set)
+        ids = torch.full((S, k), -1, dtype=torch.int64, device=dev)
+        out = torch.full((S, k), float("-inf"), dtype=torch.float32, device=dev)
+        counts = torch.zeros(S, dtype=torch.int64, device=dev)
+        starts = np.concatenate([[0], np.cumsum(counts_host)])
+        for lo, hi in plan_chunks(counts_host, int(max_pairs)):
+            total = int(starts[hi] - starts[lo])
+            if total == 0:
+                continue
+            pairs = fill(lo, hi, total)
+            lg = evaluate.score_edges(model, score_func, pairs, batch_size, h=h, test_set=test_set, logits=True)
+            seg_ptr = torch.from_numpy(starts[lo:hi + 1] - starts[lo]).to(dev)
+            ids[lo:hi], out[lo:hi], counts[lo:hi] = segment_topk(seg_ptr, lg, pairs[1], k)
+        if not logits:
+            out = torch.where(ids >= 0, torch.sigmoid(out), out)
+    return Recommendations(ids, out, counts, n_cand)
