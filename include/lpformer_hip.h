@@ -34,7 +34,7 @@ extern "C" {
 #define LPF_ERR_LAUNCH (-3)      /* hipLaunch / runtime error (see lpf_last_hip_error)  */
 #define LPF_ERR_NO_DEVICE (-4)   /* no gfx950 device visible                            */
 
-#define LPF_ABI_VERSION 11
+#define LPF_ABI_VERSION 12
 
 /* GEMM / row-wise epilogue flags */
 #define LPF_FLAG_RELU 1u
@@ -754,6 +754,58 @@ int lpf_rec_candidate_fill(int64_t S, int64_t n, const int64_t *sources, const i
  * float atomics.  scratch: int32[S + 1].  1 <= k <= LPF_TOPK_MAX_K. */
 int lpf_segment_topk_f32(int64_t S, const int64_t *seg_ptr, const float *score, const int64_t *cand, int32_t k,
                          int32_t *scratch, int64_t *ids, float *scores, int64_t *counts, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * HeaRT-style hard negatives (twohop.hip): rows of A diag(w) A, the candidate pool of a node, the rank interleave.
+ * The reference only reads such negatives from files (src/util/read_datasets.py:132-146); nothing there makes them.
+ * ---------------------------------------------------------------------------------------------- */
+/* Sources whose expansion (sum over w in N(u) of deg(w)) exceeds this get a workgroup with dense state in the
+ * workspace; the others one wavefront with the accumulators hashed in LDS.  It is also the largest threshold: a
+ * larger split_threshold (or a negative one) selects it. */
+#define LPF_TWOHOP_SPLIT_DEFAULT 512
+/* Bytes of workspace for n_groups resident workgroups: per group and node an fp64 aa, an fp64 ra, an int32 cn and an
+ * int32 stamp. */
+int64_t lpf_twohop_workspace_bytes(int64_t n, int64_t n_groups);
+/* Row u = sources[s] of A diag(w) A on a CSR with sorted, unique columns (values ignored): for each w in N(u) in
+ * ascending order, for each c in N(w): cn[c] += 1, aa[c] += w_aa[w], ra[c] += w_ra[w]; fp64 sums in that order, rounded
+ * to fp32 once; no float atomics.  The row holds the touched c in ascending id; flags bit 0 drops the members of N(u),
+ * bit 1 drops u.  Sources outside [0, n) have an empty row.  The count pass writes the row lengths; the caller scans
+ * them into offset (first output slot of each source, T slots in all) and the fill pass writes out_col and whichever
+ * of out_cn / out_aa / out_ra is not NULL.  Both passes take the same split_threshold and flags.  scratch: int32[S + 1];
+ * workspace: lpf_twohop_workspace_bytes(n, n_groups) bytes, 16-byte aligned, 1 <= n_groups <= 65535. */
+int lpf_twohop_count(int64_t S, int64_t n, const int64_t *sources, const int64_t *rowptr, const int32_t *col,
+                     int32_t split_threshold, int32_t flags, int32_t *scratch, void *workspace, int64_t n_groups,
+                     int64_t *count, void *stream);
+int lpf_twohop_fill(int64_t S, int64_t n, const int64_t *sources, const int64_t *rowptr, const int32_t *col,
+                    const float *w_aa, const float *w_ra, int32_t split_threshold, int32_t flags, int32_t *scratch,
+                    void *workspace, int64_t n_groups, const int64_t *offset, int64_t T, int32_t *out_col,
+                    int32_t *out_cn, float *out_aa, float *out_ra, void *stream);
+/* Pool of node u = nodes[i]: its two-hop row a_* (segment [a_ptr[i], a_ptr[i + 1]), built with flags = 3) united with
+ * the stored entries of its row of the PPR CSR b_*, minus its row of the adjacency exc_*, minus u; ascending id.
+ * lpf_pool_extra_count writes the number of PPR entries the two-hop row lacks; the caller scans them into x_ptr
+ * (int64[U + 1], X = x_ptr[U]).  lpf_pool_fill writes those entries to the temporaries x_col / x_val and the pool to
+ * pairs (int64 [2, T]: u, member; T = a_ptr[U] + X, the pool of node i at a_ptr[i] + x_ptr[i]) with the member's values
+ * in whichever of out_cn / out_aa / out_ra / out_ppr is not NULL (cn as float; 0 where the row does not hold it). */
+int lpf_pool_extra_count(int64_t U, int64_t n, const int64_t *nodes, const int64_t *a_ptr, const int32_t *a_col,
+                         const int64_t *b_rowptr, const int32_t *b_col, const int64_t *exc_rowptr,
+                         const int32_t *exc_col, int64_t *count, void *stream);
+int lpf_pool_fill(int64_t U, int64_t n, const int64_t *nodes, const int64_t *a_ptr, const int32_t *a_col,
+                  const int32_t *a_cn, const float *a_aa, const float *a_ra, const int64_t *b_rowptr,
+                  const int32_t *b_col, const float *b_val, const int64_t *exc_rowptr, const int32_t *exc_col,
+                  const int64_t *x_ptr, int32_t *x_col, float *x_val, int64_t X, int64_t T, int64_t *pairs,
+                  float *out_cn, float *out_aa, float *out_ra, float *out_ppr, void *stream);
+/* Largest list length of the rank interleave. */
+#define LPF_INTERLEAVE_MAX_KH 1024
+/* For node u = nodes[i]: H ranked lists ids / vals [H][U][kh] with counts [H][U] (lpf_segment_topk_f32 outputs), each
+ * cut at its first value that is not > 0.  lists[i] = the first kh distinct ids of the sequence rank 1 of list 1, rank 1
+ * of list 2, ..., rank 2 of list 1, ...; n_ranked[i] = how many that gave.  The rest is padding: draws d = 0, 1, 2, ...
+ *   x = mix32((uint32)u * 0x9E3779B1 + (uint32)seed);  x = mix32(x ^ (uint32)(seed >> 32) ^ (d * 0x85EBCA77));  c = x % n
+ *   mix32(h): h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16      (all in uint32)
+ * in order, skipping u, the members of u's row of exc_* and ids already in the list.  1 <= H <= 8,
+ * 1 <= kh <= LPF_INTERLEAVE_MAX_KH.  The caller makes sure n - 1 - deg(u) >= kh (else the tail is -1 after 2^20 draws). */
+int lpf_rank_interleave(int64_t U, int64_t n, const int64_t *nodes, int32_t H, int32_t kh, const int64_t *ids,
+                        const float *vals, const int64_t *counts, const int64_t *exc_rowptr, const int32_t *exc_col,
+                        uint64_t seed, int64_t *lists, int32_t *n_ranked, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training step of the pair stage (pair_train.hip): the forward of get_pos_encodings

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "liblpformer_hip.so")
 HOST_LIB_PATH = os.path.join(_HERE, "liblpformer_host.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 FLAG_RELU = 1
 SELECT_ERR_NODE_RANGE, SELECT_ERR_ITEM_CAP, SELECT_ERR_ENTRY_CAP = 1, 2, 4
 ROWS_PERM_LB_WORDS = 1025      # LPF_ROWS_PERM_LB_WORDS (include/lpformer_hip.h)
@@ -98,6 +98,13 @@ HIP_PROTOTYPES = {
     "lpf_rec_candidate_count": [i64, i64, vp, vp, vp, vp, f32, vp, vp, i32, i32, vp, vp, vp],
     "lpf_rec_candidate_fill": [i64, i64, vp, vp, vp, vp, f32, vp, vp, i32, i32, vp, vp, i64, vp, vp],
     "lpf_segment_topk_f32": [i64, vp, vp, vp, i32, vp, vp, vp, vp, vp],
+    "lpf_twohop_workspace_bytes": [i64, i64],
+    "lpf_twohop_count": [i64, i64, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp],
+    "lpf_twohop_fill": [i64, i64, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp],
+    "lpf_pool_extra_count": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "lpf_pool_fill": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp,
+                      vp],
+    "lpf_rank_interleave": [i64, i64, vp, i32, i32, vp, vp, vp, vp, vp, u64, vp, vp, vp],
     "lpf_ppr_push_workspace_bytes": [i64, i64, C.c_double, C.c_double],
     "lpf_ppr_push_f64": [i64, vp, vp, C.c_double, C.c_double, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp],
     "lpf_ppr_pack_workspace_bytes": [i64, i64],
@@ -123,7 +130,7 @@ HOST_PROTOTYPES = {
     "lpf_host_abi_version": [],
 }
 _RESTYPE = {"lpf_strerror": C.c_char_p, "lpf_last_hip_error": C.c_char_p, "lpf_host_free": None,
-            "lpf_ppr_push_workspace_bytes": C.c_int64, "lpf_select_plan_blocks": C.c_int64, "lpf_ppr_pack_workspace_bytes": C.c_int64,
+            "lpf_ppr_push_workspace_bytes": C.c_int64, "lpf_twohop_workspace_bytes": C.c_int64, "lpf_select_plan_blocks": C.c_int64, "lpf_ppr_pack_workspace_bytes": C.c_int64,
             "lpf_gemm_tn_workspace_floats": C.c_int64, "lpf_layernorm_bwd_workspace_floats": C.c_int64,
             "lpf_train_partial_blocks": C.c_int64, "lpf_pair_rows_piece_floats": C.c_int64}
 

@@ -102,3 +102,10 @@ static inline uint32_t lpf_drop_threshold(float p) {   // keep iff bits >= thres
     const double t = (double)p * 4294967296.0;
     return t <= 0.0 ? 0u : (t >= 4294967295.0 ? 4294967295u : (uint32_t)t);
 }
+
+// Padding draw d of node u (lpf_rank_interleave; restated in include/lpformer_hip.h): plain uint32 arithmetic.
+__host__ __device__ __forceinline__ uint32_t lpf_pad_draw(uint64_t seed, int64_t u, uint32_t d, uint32_t n) {
+    uint32_t x = lpf_mix32((uint32_t)u * 0x9E3779B1u + (uint32_t)seed);
+    x = lpf_mix32(x ^ (uint32_t)(seed >> 32) ^ (d * 0x85EBCA77u));
+    return x % n;
+}

@@ -157,13 +157,18 @@ def pair_heuristics(source, edges, *, test_set: bool = False, kinds=("cn", "aa",
                                                         ptr(ppr.val), ptr(v), st), "lpf_csr_lookup_f32")
                 out[name] = v
         if "feat" in kinds:
-            xd = _device_features(x, dev)
-            n = xd.shape[0]
-            feat = torch.empty(P, dtype=torch.float32, device=dev)
-            for lo in range(0, P, chunk):     # ids outside [0, n) give 0, as for cn / aa / ra (and nothing is read back)
-                a, b = batch[0, lo:lo + chunk], batch[1, lo:lo + chunk]
-                ok = (a >= 0) & (a < n) & (b >= 0) & (b < n)
-                cos = torch.nn.functional.cosine_similarity(xd[a.clamp(0, n - 1)], xd[b.clamp(0, n - 1)], dim=1)
-                feat[lo:lo + a.numel()] = torch.where(ok, cos, torch.zeros_like(cos))
-            out["feat"] = feat
+            out["feat"] = feature_cosine(_device_features(x, dev), batch, chunk)
     return out
+
+
+def feature_cosine(xd: torch.Tensor, batch: torch.Tensor, chunk: int = 1 << 20) -> torch.Tensor:
+    """The ``"feat"`` values of device pairs ``batch`` ([2, P] int64): cosine similarity of the rows of ``xd`` (fp32, on
+    the same device), ``chunk`` pairs at a time."""
+    n, P = xd.shape[0], batch.shape[1]
+    feat = torch.empty(P, dtype=torch.float32, device=batch.device)
+    for lo in range(0, P, chunk):     # ids outside [0, n) give 0, as for cn / aa / ra (and nothing is read back)
+        a, b = batch[0, lo:lo + chunk], batch[1, lo:lo + chunk]
+        ok = (a >= 0) & (a < n) & (b >= 0) & (b < n)
+        cos = torch.nn.functional.cosine_similarity(xd[a.clamp(0, n - 1)], xd[b.clamp(0, n - 1)], dim=1)
+        feat[lo:lo + a.numel()] = torch.where(ok, cos, torch.zeros_like(cos))
+    return feat

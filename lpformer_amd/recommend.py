@@ -26,7 +26,7 @@ from . import _lib, graph
 from ._lib import check, ptr
 
 MAX_K = 1024                 # LPF_TOPK_MAX_K (include/lpformer_hip.h)
-CANDIDATE_MODES = ("ppr", "all")
+CANDIDATE_MODES = ("ppr", "all", "2hop")
 
 
 class Recommendations(NamedTuple):
@@ -139,6 +139,19 @@ def generate_candidates(n: int, sources: torch.Tensor, include, min_ppr: float, 
     return counts, fill
 
 
+def twohop_candidates(adj, sources: torch.Tensor, exclude_adj: bool, exclude_self: bool, split_threshold: int = -1):
+    """``generate_candidates`` for ``candidates="2hop"``: every v with a common neighbour with u on ``adj`` (one row of
+    A A, ``lpf_twohop_count`` / ``lpf_twohop_fill``), minus N(u) with ``exclude_adj``, minus u with ``exclude_self``."""
+    from .hard_negatives import _TwoHop
+    th = _TwoHop(adj, sources, (), (1 if exclude_adj else 0) | (2 if exclude_self else 0), split_threshold)
+
+    def fill(lo: int, hi: int, total: int) -> torch.Tensor:
+        seg, col, _, _, _ = th.fill(lo, hi, total)
+        return torch.stack([sources[lo:hi].repeat_interleave(th.counts[lo:hi], output_size=total),
+                            col.to(torch.int64)])
+    return th.counts, fill
+
+
 def segment_topk(seg_ptr: torch.Tensor, score: torch.Tensor, cand: torch.Tensor, k: int):
     """(ids int64 [S, k], scores float32 [S, k], counts int64 [S]) of the segments ``seg_ptr`` (int64 [S + 1]) of
     ``score`` (float32) / ``cand`` (int64): the top min(k, len) of each segment by score, ties to the earlier position,
@@ -169,7 +182,8 @@ def recommend(model, score_func, sources, k: int = 100, *, candidates="ppr", min
     """The ``k`` highest-scoring candidates v of every source u in ``sources`` (int [S], host or device; duplicates are
     independent rows).
 
-    ``candidates``: ``"ppr"`` -- the entries of u's row of the split's PPR matrix (``data["ppr"]``, ``data["ppr_test"]``
+    ``candidates``: ``"2hop"`` -- every v that shares a neighbour with u on the split's typing adjacency (``exclude``
+    must then be ``"adj"`` or None; ``split_threshold`` is the two-hop kernel's); ``"ppr"`` -- the entries of u's row of the split's PPR matrix (``data["ppr"]``, ``data["ppr_test"]``
     with ``test_set``) whose fp32 value is > 0 and >= ``min_ppr``; ``"all"`` -- every node; or an int tensor [S, M] of
     explicit candidates, taken as given (no exclusion, duplicates kept).  ``exclude``: ``"adj"`` (the model's typing
     adjacency of the split), None, a ``graph.CSR`` or a ``graph.DeviceCSR``; ``exclude_self`` drops v = u.
@@ -208,8 +222,15 @@ def recommend(model, score_func, sources, k: int = 100, *, candidates="ppr", min
             include = None
             if candidates == "ppr":
                 include = model._device_graph("ppr", model._data_obj("ppr", test_set))
-            exc = _exclusion(model, exclude, test_set, dev)
-            n_cand, fill = generate_candidates(n, src, include, min_ppr, exc, exclude_self, split_threshold)
+            if candidates == "2hop":
+                if exclude not in ("adj", None):
+                    raise ValueError("candidates='2hop' takes exclude='adj' or None: the two-hop row kernel drops the "
+                                     "row of the adjacency it walks")
+                n_cand, fill = twohop_candidates(model._device_graph("mask", model._data_obj("mask", test_set)), src,
+                                                 exclude == "adj", exclude_self, split_threshold)
+            else:
+                exc = _exclusion(model, exclude, test_set, dev)
+                n_cand, fill = generate_candidates(n, src, include, min_ppr, exc, exclude_self, split_threshold)
             counts_host = n_cand.cpu().numpy()       # the one read-back: it sizes the chunks and their outputs
         if h is None:
             h = model.propagate(test_set=test_set)
