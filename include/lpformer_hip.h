@@ -3,7 +3,7 @@
  *
  * Two shared objects export these symbols:
  *   liblpformer_hip.so   (hipcc, --offload-arch=gfx950)  every entry point taking a stream
- *   liblpformer_host.so  (g++ -fopenmp)                   lpf_ppr_push_cpu, lpf_host_free, lpf_host_abi_version
+ *   liblpformer_host.so  (g++ -fopenmp)                   lpf_ppr_push_cpu, lpf_ppr_push_cpu_sources, lpf_host_free, lpf_host_abi_version
  *
  * The reference (HarryShomer/LPFormer) is 100 % Python and has no FFI of its own; each entry point
  * below therefore cites the reference Python it replaces (paths relative to the reference repo root)
@@ -34,7 +34,7 @@ extern "C" {
 #define LPF_ERR_LAUNCH (-3)      /* hipLaunch / runtime error (see lpf_last_hip_error)  */
 #define LPF_ERR_NO_DEVICE (-4)   /* no gfx950 device visible                            */
 
-#define LPF_ABI_VERSION 12
+#define LPF_ABI_VERSION 13
 
 /* GEMM / row-wise epilogue flags */
 #define LPF_FLAG_RELU 1u
@@ -667,11 +667,47 @@ int lpf_ppr_push_f64(int64_t n, const int64_t *rowptr, const int32_t *col, doubl
                      int64_t n_waves, void *workspace, int64_t workspace_bytes, int32_t *pool_col, float *pool_val,
                      int64_t pool_capacity, int64_t *row_off, int32_t *row_len, int64_t *counters, void *stream);
 
+/* The same push for the sources `sources[0 .. n_src)` only (device memory, ids in [0, n), STRICTLY ASCENDING: the dense
+ * state is stamped with the source id).  row_off / row_len are indexed by LIST POSITION (n_src entries); everything
+ * else as lpf_ppr_push_f64, with which it shares the kernel body.  Size n_waves by the list, not by n: the state that
+ * is cleared per call is 32 n bytes per wavefront. */
+int lpf_ppr_push_f64_sources(int64_t n, const int64_t *rowptr, const int32_t *col, int64_t n_src,
+                             const int32_t *sources, double alpha, double eps, int64_t n_waves, void *workspace,
+                             int64_t workspace_bytes, int32_t *pool_col, float *pool_val, int64_t pool_capacity,
+                             int64_t *row_off, int32_t *row_len, int64_t *counters, void *stream);
+
 /* Sort every row by column and pack the CSR (out_rowptr int64[n+1], out_col/out_val [nnz], nnz = counters[1] above). */
 int64_t lpf_ppr_pack_workspace_bytes(int64_t n, int64_t nnz);
 int lpf_ppr_pack_csr(int64_t n, const int64_t *row_off, const int32_t *row_len, const int32_t *pool_col,
                      const float *pool_val, int64_t nnz, int64_t *out_rowptr, int32_t *out_col, float *out_val,
                      void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Incremental refresh of the PPR matrix after a graph edit (csrc/ppr_update.hip; lpformer_amd/graph_update.py).
+ * A row of the matrix holds every node its push popped, so a row without any KEY node (endpoints of added / removed
+ * edges, old neighbours of removal endpoints) is bit-identical on the edited graph: only the other rows are pushed
+ * again (lpf_ppr_push_f64_sources) and spliced into the old CSR.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* flag[i] = 1 when row i of the CSR (rowptr int64[n+1], col int32) holds a node whose bit is set in key_bitmap
+ * (uint32[(n + 31) / 32], node v = bit v & 31 of word v >> 5), else 0; list = the flagged row ids ascending (room for
+ * n), *count = how many (device memory; nothing is read back).  bitmap_mode: 1 = every workgroup stages the bitmap in
+ * LDS (n <= 524,288), 0 = probes in global memory, -1 = LDS up to 40 KiB of bitmap. */
+int64_t lpf_ppr_affected_workspace_bytes(int64_t n);
+int lpf_ppr_affected_rows(int64_t n, const int64_t *rowptr, const int32_t *col, const uint32_t *key_bitmap,
+                          int32_t bitmap_mode, int32_t *flag, int32_t *list, int64_t *count, void *workspace,
+                          int64_t workspace_bytes, void *stream);
+
+/* New CSR from the old one and the re-pushed rows of `sources[0 .. n_src)` (distinct ids; row_off / row_len / pool_* as
+ * lpf_ppr_push_f64_sources left them, nnz_pool = its counters[1]): row i is the old row, or, for a listed source, its
+ * new row sorted by column.  out_capacity = entries out_col / out_val have room for; the caller sizes it as
+ * old nnz - (old lengths of the listed rows) + nnz_pool, rows that would pass it are not written. */
+int64_t lpf_ppr_splice_workspace_bytes(int64_t n, int64_t n_src, int64_t nnz_pool);
+int lpf_ppr_splice_csr(int64_t n, const int64_t *old_rowptr, const int32_t *old_col, const float *old_val,
+                       int64_t n_src, const int32_t *sources, const int64_t *row_off, const int32_t *row_len,
+                       const int32_t *pool_col, const float *pool_val, int64_t nnz_pool, int64_t *out_rowptr,
+                       int32_t *out_col, float *out_val, int64_t out_capacity, void *workspace,
+                       int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Per-model indexes over the PPR matrix, built on the device.  Selection results are identical
@@ -866,6 +902,12 @@ int lpf_pair_scatter_add_f32(int64_t bs, int32_t D, const int64_t *batch, int64_
  * rows sorted by column; release both with lpf_host_free. */
 int lpf_ppr_push_cpu(int64_t n, const int64_t *indptr_host, const int32_t *indices_host, double alpha, double eps,
                      int64_t *out_rowptr_host, int32_t **out_col_host, float **out_val_host, int32_t num_threads);
+
+/* The same push for the sources `sources_host[0 .. n_src)` only (ids in [0, n), strictly ascending): out_rowptr is
+ * int64[n_src + 1] and row k of the result belongs to the k-th source.  Host twin of lpf_ppr_push_f64_sources. */
+int lpf_ppr_push_cpu_sources(int64_t n, const int64_t *indptr_host, const int32_t *indices_host, double alpha,
+                             double eps, int64_t n_src, const int32_t *sources_host, int64_t *out_rowptr_host,
+                             int32_t **out_col_host, float **out_val_host, int32_t num_threads);
 
 void lpf_host_free(void *p);
 int lpf_host_abi_version(void);

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "liblpformer_hip.so")
 HOST_LIB_PATH = os.path.join(_HERE, "liblpformer_host.so")
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 FLAG_RELU = 1
 SELECT_ERR_NODE_RANGE, SELECT_ERR_ITEM_CAP, SELECT_ERR_ENTRY_CAP = 1, 2, 4
 ROWS_PERM_LB_WORDS = 1025      # LPF_ROWS_PERM_LB_WORDS (include/lpformer_hip.h)
@@ -107,6 +107,11 @@ HIP_PROTOTYPES = {
     "lpf_rank_interleave": [i64, i64, vp, i32, i32, vp, vp, vp, vp, vp, u64, vp, vp, vp],
     "lpf_ppr_push_workspace_bytes": [i64, i64, C.c_double, C.c_double],
     "lpf_ppr_push_f64": [i64, vp, vp, C.c_double, C.c_double, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp],
+    "lpf_ppr_push_f64_sources": [i64, vp, vp, i64, vp, C.c_double, C.c_double, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp],
+    "lpf_ppr_affected_workspace_bytes": [i64],
+    "lpf_ppr_affected_rows": [i64, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp],
+    "lpf_ppr_splice_workspace_bytes": [i64, i64, i64],
+    "lpf_ppr_splice_csr": [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, i64, vp],
     "lpf_ppr_pack_workspace_bytes": [i64, i64],
     "lpf_ppr_pack_csr": [i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp],
     "lpf_train_partial_blocks": [i64],
@@ -126,11 +131,13 @@ HIP_PROTOTYPES = {
 }
 HOST_PROTOTYPES = {
     "lpf_ppr_push_cpu": [i64, vp, vp, f64, f64, vp, C.POINTER(vp), C.POINTER(vp), i32],
+    "lpf_ppr_push_cpu_sources": [i64, vp, vp, f64, f64, i64, vp, vp, C.POINTER(vp), C.POINTER(vp), i32],
     "lpf_host_free": [vp],
     "lpf_host_abi_version": [],
 }
 _RESTYPE = {"lpf_strerror": C.c_char_p, "lpf_last_hip_error": C.c_char_p, "lpf_host_free": None,
             "lpf_ppr_push_workspace_bytes": C.c_int64, "lpf_twohop_workspace_bytes": C.c_int64, "lpf_select_plan_blocks": C.c_int64, "lpf_ppr_pack_workspace_bytes": C.c_int64,
+            "lpf_ppr_affected_workspace_bytes": C.c_int64, "lpf_ppr_splice_workspace_bytes": C.c_int64,
             "lpf_gemm_tn_workspace_floats": C.c_int64, "lpf_layernorm_bwd_workspace_floats": C.c_int64,
             "lpf_train_partial_blocks": C.c_int64, "lpf_pair_rows_piece_floats": C.c_int64}
 

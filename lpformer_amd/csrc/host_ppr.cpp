@@ -34,15 +34,10 @@ struct Arena {
     std::vector<RowRef> rows;
 };
 
-}  // namespace
-
-extern "C" int lpf_ppr_push_cpu(int64_t n, const int64_t *indptr, const int32_t *indices, double alpha, double eps,
-                                int64_t *out_rowptr, int32_t **out_col, float **out_val, int32_t num_threads) {
-    if (n < 0 || !indptr || (!indices && n > 0 && indptr[n] > 0) || !out_rowptr || !out_col || !out_val)
-        return LPF_ERR_INVALID;
-    *out_col = nullptr;
-    *out_val = nullptr;
-    if (n >= (1ll << 31)) return LPF_ERR_UNSUPPORTED;
+// The push for the sources `sources[0 .. n_src)` (nullptr: the sources 0 .. n_src - 1); output row k belongs to the
+// k-th source.
+int push_rows(int64_t n, const int64_t *indptr, const int32_t *indices, double alpha, double eps, int64_t n_src,
+              const int32_t *sources, int64_t *out_rowptr, int32_t **out_col, float **out_val, int32_t num_threads) {
     const int nt = num_threads > 0 ? num_threads : omp_get_max_threads();
     const double alpha_eps = alpha * eps;
     std::vector<Arena> arenas((size_t)nt);
@@ -57,8 +52,8 @@ extern "C" int lpf_ppr_push_cpu(int64_t n, const int64_t *indptr, const int32_t 
         std::vector<std::pair<int32_t, float>> rowbuf;
 
 #pragma omp for schedule(dynamic, 32)
-        for (int64_t src64 = 0; src64 < n; ++src64) {
-            const int32_t src = (int32_t)src64;
+        for (int64_t src64 = 0; src64 < n_src; ++src64) {
+            const int32_t src = sources ? sources[src64] : (int32_t)src64;
             touched.clear();
             stack.clear();
             p[src] = 0.0;  // p = {src: 0.0}
@@ -112,11 +107,11 @@ extern "C" int lpf_ppr_push_cpu(int64_t n, const int64_t *indptr, const int32_t 
         }
     }
 
-    std::fill(out_rowptr, out_rowptr + n + 1, (int64_t)0);
+    std::fill(out_rowptr, out_rowptr + n_src + 1, (int64_t)0);
     for (const Arena &ar : arenas)
         for (const RowRef &rr : ar.rows) out_rowptr[rr.row + 1] = rr.len;
-    for (int64_t i = 0; i < n; ++i) out_rowptr[i + 1] += out_rowptr[i];
-    const int64_t nnz = out_rowptr[n];
+    for (int64_t i = 0; i < n_src; ++i) out_rowptr[i + 1] += out_rowptr[i];
+    const int64_t nnz = out_rowptr[n_src];
     int32_t *col = (int32_t *)malloc(sizeof(int32_t) * (size_t)std::max<int64_t>(nnz, 1));
     float *val = (float *)malloc(sizeof(float) * (size_t)std::max<int64_t>(nnz, 1));
     if (!col || !val) {
@@ -135,6 +130,38 @@ extern "C" int lpf_ppr_push_cpu(int64_t n, const int64_t *indptr, const int32_t 
     *out_col = col;
     *out_val = val;
     return LPF_OK;
+}
+
+}  // namespace
+
+extern "C" int lpf_ppr_push_cpu(int64_t n, const int64_t *indptr, const int32_t *indices, double alpha, double eps,
+                                int64_t *out_rowptr, int32_t **out_col, float **out_val, int32_t num_threads) {
+    if (n < 0 || !indptr || (!indices && n > 0 && indptr[n] > 0) || !out_rowptr || !out_col || !out_val)
+        return LPF_ERR_INVALID;
+    *out_col = nullptr;
+    *out_val = nullptr;
+    if (n >= (1ll << 31)) return LPF_ERR_UNSUPPORTED;
+    return push_rows(n, indptr, indices, alpha, eps, n, nullptr, out_rowptr, out_col, out_val, num_threads);
+}
+
+extern "C" int lpf_ppr_push_cpu_sources(int64_t n, const int64_t *indptr, const int32_t *indices, double alpha,
+                                        double eps, int64_t n_src, const int32_t *sources, int64_t *out_rowptr,
+                                        int32_t **out_col, float **out_val, int32_t num_threads) {
+    if (n < 0 || !indptr || (!indices && n > 0 && indptr[n] > 0) || !out_rowptr || !out_col || !out_val || n_src < 0 ||
+        n_src > n || (n_src > 0 && !sources))
+        return LPF_ERR_INVALID;
+    *out_col = nullptr;
+    *out_val = nullptr;
+    if (n >= (1ll << 31)) return LPF_ERR_UNSUPPORTED;
+    for (int64_t k = 0; k < n_src; ++k)  // strictly ascending ids in [0, n): the epoch stamp is the source id
+        if (sources[k] < 0 || sources[k] >= n || (k > 0 && sources[k] <= sources[k - 1])) return LPF_ERR_INVALID;
+    if (n_src == 0) {
+        out_rowptr[0] = 0;
+        *out_col = (int32_t *)malloc(sizeof(int32_t));
+        *out_val = (float *)malloc(sizeof(float));
+        return (*out_col && *out_val) ? LPF_OK : LPF_ERR_INVALID;
+    }
+    return push_rows(n, indptr, indices, alpha, eps, n_src, sources, out_rowptr, out_col, out_val, num_threads);
 }
 
 extern "C" void lpf_host_free(void *p) { free(p); }

@@ -52,8 +52,12 @@ struct alignas(16) PprEntry {
     int64_t e0;
 };
 
+// LIST = false: the sources are 0 .. n_src - 1 (n_src = n) and row_off / row_len are indexed by source id;
+// LIST = true: the sources are sources[0 .. n_src) (strictly ascending ids: the epoch stamp of the dense state is the
+// source id, so an id must not come twice) and row_off / row_len are indexed by LIST POSITION.
+template <bool LIST>
 __global__ __launch_bounds__(256) void ppr_push_kernel(
-    int64_t n, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, double alpha, double alpha_eps,
+    int64_t n, int64_t n_src, const int32_t *__restrict__ sources, const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, double alpha, double alpha_eps,
     PprR *__restrict__ r_all, PprP *__restrict__ p_all, PprEntry *__restrict__ stack_all,
     int32_t *__restrict__ touched_all, int64_t list_cap, unsigned long long *__restrict__ counters,
     int32_t *__restrict__ pool_col, float *__restrict__ pool_val, int64_t pool_cap, int64_t *__restrict__ row_off,
@@ -70,8 +74,17 @@ __global__ __launch_bounds__(256) void ppr_push_kernel(
         int64_t src64 = 0;
         if (lane == 0) src64 = (int64_t)atomicAdd(&counters[0], 1ull);
         src64 = wave_bcast_i64(src64);
-        if (src64 >= n) break;
-        const int32_t src = (int32_t)src64;
+        if (src64 >= n_src) break;
+        const int64_t slot = src64;  // where the row's offset and length go
+        const int32_t src = LIST ? sources[src64] : (int32_t)src64;
+        if (LIST && (uint32_t)src >= (uint32_t)n) {  // an id outside the graph: an empty row, nothing touched
+            if (lane == 0) {
+                row_off[slot] = 0;
+                row_len[slot] = 0;
+                atomicAdd(&counters[2], 1ull);
+            }
+            continue;
+        }
         const int64_t s0 = rowptr[src], s1 = rowptr[src + 1];
         if (lane == 0) {  // p = {src: 0.0}; r = {src: alpha}; q = [src]
             P[src] = PprP{0.0, src, 0};
@@ -145,8 +158,8 @@ __global__ __launch_bounds__(256) void ppr_push_kernel(
         if (lane == 0) off = (int64_t)atomicAdd(&counters[1], (unsigned long long)nt);
         off = wave_bcast_i64(off);
         if (lane == 0) {
-            row_off[src] = off;
-            row_len[src] = (int32_t)nt;
+            row_off[slot] = off;
+            row_len[slot] = (int32_t)nt;
             if (overflow) atomicAdd(&counters[2], 1ull);
         }
         if (off + nt <= pool_cap && !overflow) {
@@ -203,11 +216,12 @@ extern "C" int64_t lpf_ppr_push_workspace_bytes(int64_t n, int64_t n_waves, doub
            align256(n_waves * cap * (int64_t)sizeof(PprEntry)) + align256(n_waves * cap * 4) + 256;
 }
 
-extern "C" int lpf_ppr_push_f64(int64_t n, const int64_t *rowptr, const int32_t *col, double alpha, double eps,
-                                int64_t n_waves, void *workspace, int64_t workspace_bytes, int32_t *pool_col,
-                                float *pool_val, int64_t pool_capacity, int64_t *row_off, int32_t *row_len,
-                                int64_t *counters, void *stream) {
-    if (n == 0) return LPF_OK;
+namespace {
+
+int ppr_push_launch(int64_t n, int64_t n_src, const int32_t *sources, const int64_t *rowptr, const int32_t *col,
+                    double alpha, double eps, int64_t n_waves, void *workspace, int64_t workspace_bytes,
+                    int32_t *pool_col, float *pool_val, int64_t pool_capacity, int64_t *row_off, int32_t *row_len,
+                    int64_t *counters, void *stream) {
     LPF_REQUIRE(n > 0 && n < (1ll << 31) && rowptr && col && alpha > 0.0 && alpha < 1.0 && eps > 0.0 && n_waves > 0 &&
                 (n_waves & 3) == 0 && workspace && pool_col && pool_val && pool_capacity >= 0 && row_off && row_len &&
                 counters && lpf_aligned16(workspace));
@@ -227,11 +241,45 @@ extern "C" int lpf_ppr_push_f64(int64_t n, const int64_t *rowptr, const int32_t 
         hipMemsetAsync(P, 0xFF, (size_t)(n_waves * n) * sizeof(PprP), s) != hipSuccess ||
         hipMemsetAsync(counters, 0, 4 * sizeof(int64_t), s) != hipSuccess)
         return LPF_ERR_LAUNCH;
-    hipLaunchKernelGGL(ppr_push_kernel, dim3((unsigned)(n_waves / 4)), dim3(256), 0, s, n, rowptr, col, alpha,
-                       alpha * eps, R, P, stack, touched, cap, reinterpret_cast<unsigned long long *>(counters),
-                       pool_col, pool_val, pool_capacity, row_off, row_len);
+    const dim3 grid((unsigned)(n_waves / 4));
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(counters);
+    if (sources)
+        hipLaunchKernelGGL(ppr_push_kernel<true>, grid, dim3(256), 0, s, n, n_src, sources, rowptr, col, alpha,
+                           alpha * eps, R, P, stack, touched, cap, cnt, pool_col, pool_val, pool_capacity, row_off,
+                           row_len);
+    else
+        hipLaunchKernelGGL(ppr_push_kernel<false>, grid, dim3(256), 0, s, n, n_src, sources, rowptr, col, alpha,
+                           alpha * eps, R, P, stack, touched, cap, cnt, pool_col, pool_val, pool_capacity, row_off,
+                           row_len);
     LPF_CHECK_LAUNCH();
     return LPF_OK;
+}
+
+}  // namespace
+
+extern "C" int lpf_ppr_push_f64(int64_t n, const int64_t *rowptr, const int32_t *col, double alpha, double eps,
+                                int64_t n_waves, void *workspace, int64_t workspace_bytes, int32_t *pool_col,
+                                float *pool_val, int64_t pool_capacity, int64_t *row_off, int32_t *row_len,
+                                int64_t *counters, void *stream) {
+    if (n == 0) return LPF_OK;
+    return ppr_push_launch(n, n, nullptr, rowptr, col, alpha, eps, n_waves, workspace, workspace_bytes, pool_col,
+                           pool_val, pool_capacity, row_off, row_len, counters, stream);
+}
+
+extern "C" int lpf_ppr_push_f64_sources(int64_t n, const int64_t *rowptr, const int32_t *col, int64_t n_src,
+                                        const int32_t *sources, double alpha, double eps, int64_t n_waves,
+                                        void *workspace, int64_t workspace_bytes, int32_t *pool_col, float *pool_val,
+                                        int64_t pool_capacity, int64_t *row_off, int32_t *row_len, int64_t *counters,
+                                        void *stream) {
+    LPF_REQUIRE(n_src >= 0 && n_src <= n && counters);
+    if (n_src == 0) {
+        if (hipMemsetAsync(counters, 0, 4 * sizeof(int64_t), static_cast<hipStream_t>(stream)) != hipSuccess)
+            return LPF_ERR_LAUNCH;
+        return LPF_OK;
+    }
+    LPF_REQUIRE(sources);
+    return ppr_push_launch(n, n_src, sources, rowptr, col, alpha, eps, n_waves, workspace, workspace_bytes, pool_col,
+                           pool_val, pool_capacity, row_off, row_len, counters, stream);
 }
 
 extern "C" int64_t lpf_ppr_pack_workspace_bytes(int64_t n, int64_t nnz) {

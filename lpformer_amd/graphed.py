@@ -56,6 +56,14 @@ class GraphedScorer:
         return tuple((p.data_ptr(), p._version) for p in self._params) + (self.model.precision,
                                                                            self.model.tail_precision)
 
+    def _check_graph(self):
+        """A scorer holds pointers into the graph indexes (and an encoder output) of the graph it was recorded on:
+        after ``graph_update.update_graph`` replaced the model's graph it must not score any more."""
+        if getattr(self.model, "_graph_epoch", 0) != self._graph_epoch:
+            from ._lib import LpfError
+            raise LpfError("the model's graph was replaced by update_graph after this scorer was recorded; build a new "
+                           "scorer from the new encoder output (model.propagate())")
+
     def stale(self) -> bool:
         """True when a parameter (storage or version) or a precision switch changed since the capture."""
         return self._param_key() != self._key
@@ -63,6 +71,7 @@ class GraphedScorer:
     def _capture(self):
         model, dev = self.model, self.model.device
         self._params = list(model.parameters()) + list(self.score_func.parameters())
+        self._graph_epoch = getattr(model, "_graph_epoch", 0)
         self.stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(self.stream):
             for _ in range(2):  # sizes the per-stream workspaces and fills every parameter-derived cache
@@ -90,6 +99,7 @@ class GraphedScorer:
         parameter changes -- it then owes one ``stale()`` per sweep."""
         if batch.shape != self.batch.shape:
             raise ValueError(f"this graph was captured for batches of shape {tuple(self.batch.shape)}")
+        self._check_graph()
         if validate and self.stale():
             self._capture()
         if batch is not self.batch:
@@ -155,6 +165,7 @@ class PlannedScorer(GraphedScorer):
         from . import _lib
         model, dev = self.model, self.model.device
         self._params = list(model.parameters()) + list(self.score_func.parameters())
+        self._graph_epoch = getattr(model, "_graph_epoch", 0)
         self.stream.wait_stream(torch.cuda.current_stream(dev))
         kw = dict(test_set=self.test_set, logits=self.logits)
         with torch.cuda.stream(self.stream):
@@ -210,6 +221,7 @@ class PlannedScorer(GraphedScorer):
         pipelines over several scorers whose ids have long been resident and whose consumer synchronises by itself."""
         if batch.shape != self.batch.shape:
             raise ValueError(f"this plan was recorded for batches of shape {tuple(self.batch.shape)}")
+        self._check_graph()
         if validate and self.stale():
             self._capture()
         cur = torch.cuda.current_stream(self.model.device) if ordered else None
