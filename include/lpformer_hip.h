@@ -34,7 +34,7 @@ extern "C" {
 #define LPF_ERR_LAUNCH (-3)      /* hipLaunch / runtime error (see lpf_last_hip_error)  */
 #define LPF_ERR_NO_DEVICE (-4)   /* no gfx950 device visible                            */
 
-#define LPF_ABI_VERSION 13
+#define LPF_ABI_VERSION 14
 
 /* GEMM / row-wise epilogue flags */
 #define LPF_FLAG_RELU 1u
@@ -842,6 +842,32 @@ int lpf_pool_fill(int64_t U, int64_t n, const int64_t *nodes, const int64_t *a_p
 int lpf_rank_interleave(int64_t U, int64_t n, const int64_t *nodes, int32_t H, int32_t kh, const int64_t *ids,
                         const float *vals, const int64_t *counts, const int64_t *exc_rowptr, const int32_t *exc_col,
                         uint64_t seed, int64_t *lists, int32_t *n_ranked, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Ranking counts (rank_metrics.hip): per positive score, the negatives that are >= it (ge) and > it (gt).  Ranks
+ * (0.5 (ge + gt) + 1, src/train/evaluation.py:23-90), Hits@K, MRR, AUC and AP follow from the two.
+ * Comparisons are IEEE, as in torch's (neg >= pos).sum(): a NaN negative is never counted, a NaN positive gets
+ * ge = gt = 0, -0.0 == +0.0, +-inf are ordinary values.  nan_counts int64[2] (device) receives the NaNs seen among
+ * the positives [0] and the negatives [1]: an overflowed selection batch scores NaN, and a metric over such scores
+ * should say so.  ge / gt are written without atomics (exact, order-free); nothing is read back.
+ * ---------------------------------------------------------------------------------------------- */
+/* pos[P] against neg[P, K] (row stride ld_neg >= 0 floats, any base alignment): one pass over the negatives, lane
+ * groups of 1 .. 64 lanes per row by K, 16-byte loads over the aligned body of every row. */
+int lpf_rank_rows_f32(int64_t P, int64_t K, const float *pos, const float *neg, int64_t ld_neg, int32_t *ge,
+                      int32_t *gt, int64_t *nan_counts, void *stream);
+/* Bytes of workspace for sorting M negatives: the unsorted keys and rocPRIM's temporary storage, O(M); independent
+ * of P (the parameter is kept so that a later layout may use it). */
+int64_t lpf_rank_shared_workspace_bytes(int64_t P, int64_t M);
+/* pos[P] against one shared set of M negatives, M <= 2^31 - 1.  sorted_keys uint32[M] belongs to the caller.
+ * neg != NULL: the negatives (unsorted) are mapped to ordered keys (-0.0 -> +0.0, NaN -> 0xFFFFFFFF, else the sign
+ * flip that makes unsigned order the IEEE order), radix-sorted into sorted_keys (workspace: 16-byte aligned,
+ * workspace_bytes >= lpf_rank_shared_workspace_bytes), and the positives ranked.  neg == NULL: sorted_keys is what an
+ * earlier call left there and only the positives are ranked (workspace unused) -- train, valid and test positives
+ * against one set of negatives sort it once.  Two lower-bound searches per positive, the top of the tree (up to 4096
+ * evenly spaced keys) in LDS. */
+int lpf_rank_shared_f32(int64_t P, const float *pos, int64_t M, const float *neg, uint32_t *sorted_keys,
+                        void *workspace, int64_t workspace_bytes, int32_t *ge, int32_t *gt, int64_t *nan_counts,
+                        void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training step of the pair stage (pair_train.hip): the forward of get_pos_encodings

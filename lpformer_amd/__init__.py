@@ -4,7 +4,9 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
     LinkTransformer, mlp_score          drop-ins for src/models/link_transformer.py / other_models.py
     LPFormer                            torch_geometric.nn.models.LPFormer-style facade (logits out)
     calc_ppr, calc_ppr_gpu, get_ppr     drop-ins for src/util/calc_ppr_scores.py (host OpenMP push / MI355X push)
-    evaluate                            encoder-once, device-resident evaluation sweep + ranking metrics (also by bin)
+    evaluate                            encoder-once, device-resident evaluation sweep + ranking metrics (also by bin);
+                                        rank_counts / ranks / sample_hits / link_metrics / split_metrics /
+                                        evaluate_model: ranks, Hits@K, MRR, AUC, AP from device rank-count kernels
     pair_heuristics                     CN / Adamic-Adar / Resource Allocation (+ PPR, feature cosine) of pairs
     recommend                           top-K new links per source node (device candidates, scoring, top-K)
     heart_negatives, twohop_rows        HeaRT-style hard negatives [P, K, 2] made on the device; rows of A diag(w) A

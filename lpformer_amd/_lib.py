@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "liblpformer_hip.so")
 HOST_LIB_PATH = os.path.join(_HERE, "liblpformer_host.so")
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 FLAG_RELU = 1
 SELECT_ERR_NODE_RANGE, SELECT_ERR_ITEM_CAP, SELECT_ERR_ENTRY_CAP = 1, 2, 4
 ROWS_PERM_LB_WORDS = 1025      # LPF_ROWS_PERM_LB_WORDS (include/lpformer_hip.h)
@@ -105,6 +105,9 @@ HIP_PROTOTYPES = {
     "lpf_pool_fill": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp,
                       vp],
     "lpf_rank_interleave": [i64, i64, vp, i32, i32, vp, vp, vp, vp, vp, u64, vp, vp, vp],
+    "lpf_rank_rows_f32": [i64, i64, vp, vp, i64, vp, vp, vp, vp],
+    "lpf_rank_shared_workspace_bytes": [i64, i64],
+    "lpf_rank_shared_f32": [i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp],
     "lpf_ppr_push_workspace_bytes": [i64, i64, C.c_double, C.c_double],
     "lpf_ppr_push_f64": [i64, vp, vp, C.c_double, C.c_double, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp],
     "lpf_ppr_push_f64_sources": [i64, vp, vp, i64, vp, C.c_double, C.c_double, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp],
@@ -139,7 +142,8 @@ _RESTYPE = {"lpf_strerror": C.c_char_p, "lpf_last_hip_error": C.c_char_p, "lpf_h
             "lpf_ppr_push_workspace_bytes": C.c_int64, "lpf_twohop_workspace_bytes": C.c_int64, "lpf_select_plan_blocks": C.c_int64, "lpf_ppr_pack_workspace_bytes": C.c_int64,
             "lpf_ppr_affected_workspace_bytes": C.c_int64, "lpf_ppr_splice_workspace_bytes": C.c_int64,
             "lpf_gemm_tn_workspace_floats": C.c_int64, "lpf_layernorm_bwd_workspace_floats": C.c_int64,
-            "lpf_train_partial_blocks": C.c_int64, "lpf_pair_rows_piece_floats": C.c_int64}
+            "lpf_train_partial_blocks": C.c_int64, "lpf_pair_rows_piece_floats": C.c_int64,
+            "lpf_rank_shared_workspace_bytes": C.c_int64}
 
 
 class LpfError(RuntimeError):

@@ -168,6 +168,305 @@ def ranking_metrics(pos: torch.Tensor, neg: torch.Tensor) -> dict:
             "Hits@100": float((rank <= 100).float().mean().item()), "MRR": float((1.0 / rank).mean().item())}
 
 
+# ------------------------------------------------------------------------------------------------ rank counts
+# Everything below follows from two integers per positive: ge = #{negatives >= it} and gt = #{negatives > it}
+# (DESIGN 5.12).  Tensors on a GPU go through lpf_rank_rows_f32 / lpf_rank_shared_f32 (csrc/rank_metrics.hip); tensors
+# on the CPU through the torch restatement in the same functions.  Comparisons are IEEE on both paths: a NaN negative
+# is never counted, a NaN positive gets ge = gt = 0, -0.0 == +0.0, +-inf are ordinary values.
+INT32_MAX = 2 ** 31 - 1
+
+
+def _raw_stream(dev) -> int:
+    return torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
+
+
+def _scores(t, what: str) -> torch.Tensor:
+    t = torch.as_tensor(t)
+    if not t.is_floating_point():
+        raise TypeError(f"{what} must be floating-point scores, got {t.dtype}")
+    return t if t.dtype == torch.float32 else t.to(torch.float32)
+
+
+class SortedNegatives:
+    """One shared set of negatives, sorted once (``sort_negatives``): rank any number of positive sets against it.
+    On a GPU ``keys`` are the ordered uint32 keys lpf_rank_shared_f32 left (stored as int32); on the CPU the sorted
+    scores without their NaNs.  ``numel`` counts every negative, NaNs included."""
+
+    def __init__(self, keys: torch.Tensor, numel: int):
+        self.keys, self.numel = keys, int(numel)
+
+    @property
+    def device(self):
+        return self.keys.device
+
+
+def _shared_call(pos: torch.Tensor, neg: Optional[torch.Tensor], keys: torch.Tensor, m: int):
+    """lpf_rank_shared_f32 on the current stream of the tensors' device.  ``neg`` None: ``keys`` are already sorted."""
+    from . import _lib
+    dev = keys.device
+    p = pos.numel()
+    ge = torch.empty(p, dtype=torch.int32, device=dev)
+    gt = torch.empty(p, dtype=torch.int32, device=dev)
+    nan = torch.empty(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        hip = _lib.hip()
+        ws, nbytes = None, 0
+        if neg is not None and m > 0:
+            nbytes = int(hip.lpf_rank_shared_workspace_bytes(p, m))
+            if nbytes <= 0:
+                raise _lib.LpfError("lpf_rank_shared_workspace_bytes: no size for this many negatives")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _lib.check(hip.lpf_rank_shared_f32(p, _lib.ptr(pos), m, _lib.ptr(neg) if m > 0 else None, _lib.ptr(keys),
+                                           _lib.ptr(ws), nbytes, _lib.ptr(ge), _lib.ptr(gt), _lib.ptr(nan),
+                                           _raw_stream(dev)), "lpf_rank_shared_f32")
+    return ge, gt, nan
+
+
+def sort_negatives(neg) -> SortedNegatives:
+    """Sort one shared set of negatives (any shape, flattened) for ``rank_counts`` / ``ranks`` / ``link_metrics``."""
+    if isinstance(neg, SortedNegatives):
+        return neg
+    neg = _scores(neg, "neg").reshape(-1).contiguous()
+    m = neg.numel()
+    if m > INT32_MAX:
+        raise ValueError(f"at most 2^31 - 1 shared negatives, got {m}")
+    if not neg.is_cuda:
+        return SortedNegatives(torch.sort(neg[~torch.isnan(neg)]).values, m)
+    keys = torch.empty(m, dtype=torch.int32, device=neg.device)
+    _shared_call(torch.empty(0, dtype=torch.float32, device=neg.device), neg, keys, m)
+    return SortedNegatives(keys, m)
+
+
+def _counts_shared(pos: torch.Tensor, sn: SortedNegatives):
+    """(ge, gt int32 [P], nan int64 [2]: NaNs among the positives and among the negatives) on the device of pos."""
+    if sn.device != pos.device:
+        raise ValueError(f"pos is on {pos.device}, the negatives on {sn.device}")
+    if pos.is_cuda:
+        return _shared_call(pos, None, sn.keys, sn.numel)
+    srt = sn.keys
+    mv = srt.numel()
+    bad = torch.isnan(pos)
+    q = torch.where(bad, torch.zeros_like(pos), pos)
+    ge = mv - torch.searchsorted(srt, q, right=False)
+    gt = mv - torch.searchsorted(srt, q, right=True)
+    ge, gt = ge.masked_fill(bad, 0).to(torch.int32), gt.masked_fill(bad, 0).to(torch.int32)
+    return ge, gt, torch.stack([bad.sum(), torch.as_tensor(sn.numel - mv)]).to(torch.int64)
+
+
+def _counts_rows(pos: torch.Tensor, neg: torch.Tensor):
+    p, k = neg.shape
+    if not pos.is_cuda:
+        col = pos.reshape(-1, 1)
+        ge = (neg >= col).sum(dim=1).to(torch.int32)
+        gt = (neg > col).sum(dim=1).to(torch.int32)
+        return ge, gt, torch.stack([torch.isnan(pos).sum(), torch.isnan(neg).sum()]).to(torch.int64)
+    from . import _lib
+    if p > INT32_MAX - 1 or k > INT32_MAX - 1:
+        raise ValueError("at most 2^31 - 2 rows and columns")
+    if k > 1 and neg.stride(1) != 1:
+        neg = neg.contiguous()
+    ld = neg.stride(0) if p > 1 else k          # (a row stride of a view is used as it is: no copy)
+    if ld < 0:
+        neg, ld = neg.contiguous(), k
+    dev = pos.device
+    ge = torch.empty(p, dtype=torch.int32, device=dev)
+    gt = torch.empty(p, dtype=torch.int32, device=dev)
+    nan = torch.empty(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.hip().lpf_rank_rows_f32(p, k, _lib.ptr(pos), _lib.ptr(neg) if k > 0 else None, ld, _lib.ptr(ge),
+                                                _lib.ptr(gt), _lib.ptr(nan), _raw_stream(dev)), "lpf_rank_rows_f32")
+    return ge, gt, nan
+
+
+def _prepare(pos, neg):
+    """(pos float32 [P] contiguous, rows [P, K] or None, SortedNegatives or None) after the shape checks."""
+    pos = _scores(pos, "pos").reshape(-1).contiguous()
+    if isinstance(neg, SortedNegatives):
+        if neg.device != pos.device:
+            raise ValueError(f"pos is on {pos.device}, the negatives on {neg.device}")
+        return pos, None, neg
+    neg = _scores(neg, "neg")
+    if neg.device != pos.device:
+        raise ValueError(f"pos is on {pos.device}, neg on {neg.device}")
+    if neg.dim() == 1:
+        return pos, None, sort_negatives(neg)
+    if neg.dim() != 2:
+        raise ValueError("neg must be 1-D (shared negatives) or [P, K] (per-positive negatives)")
+    if neg.shape[0] != pos.numel():
+        raise ValueError(f"neg [P, K] must have one row per positive ({pos.numel()}), got {tuple(neg.shape)}")
+    return pos, neg, None
+
+
+def _counts(pos, neg):
+    pos, rows, sn = _prepare(pos, neg)
+    return _counts_rows(pos, rows) if rows is not None else _counts_shared(pos, sn)
+
+
+def rank_counts(pos, neg):
+    """``(ge, gt)`` int32 [P]: per positive the number of negatives ``>=`` it and ``>`` it.  ``neg`` 1-D (or a
+    ``SortedNegatives``): one shared set, sorted once, two bound searches per positive -- the [P, M] comparison the
+    reference builds with ``neg.repeat(P, 1)`` (evaluation.py:121-125) never exists.  ``neg`` [P, K]: each positive
+    against its own row, one pass over the negatives."""
+    ge, gt, _ = _counts(pos, neg)
+    return ge, gt
+
+
+def _rank_f32(ge: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
+    return 0.5 * (ge.to(torch.int64) + gt).to(torch.float32) + 1.0   # ranking_metrics' expression
+
+
+def ranks(pos, neg) -> torch.Tensor:
+    """``get_ranking_list`` (evaluation.py:74-90): the mean of the optimistic and the pessimistic rank,
+    ``0.5 * (ge + gt) + 1`` as float32 [P]; shared negatives need no ``repeat``."""
+    ge, gt, _ = _counts(pos, neg)
+    return _rank_f32(ge, gt)
+
+
+def sample_hits(pos, neg, ks=(20, 50, 100)) -> dict:
+    """``sample_level_hits`` (evaluation.py:53-71): ``{"Hits@K": float32 [P] of 0/1}``, 1 where the rank is <= K."""
+    rank = ranks(pos, neg)
+    return {f"Hits@{k}": (rank <= k).to(torch.float32) for k in ks}
+
+
+def _check_ks(k_list):
+    ks = [int(k) for k in k_list]
+    if any(k < 1 for k in ks):
+        raise ValueError(f"every K must be >= 1, got {list(k_list)}")
+    return ks
+
+
+def _link_metrics(pos, rows, sn, ks, mrr, auc, accumulate) -> dict:
+    if accumulate not in (torch.float64, torch.float32):
+        raise ValueError("accumulate must be torch.float64 or torch.float32")
+    p = pos.numel()
+    ge, gt, nan = _counts_rows(pos, rows) if rows is not None else _counts_shared(pos, sn)
+    per_row = rows is not None
+    m = rows.shape[1] if per_row else sn.numel
+    rank32 = _rank_f32(ge, gt)
+    # Hits: the OGB rule for one shared set (ge < K  <=>  pos > K-th largest negative; all ones when M < K), the
+    # reference's rank <= K for per-row negatives (evaluate_mrr)
+    hit = [(rank32 <= k) if per_row else (ge < k) for k in ks]
+    ints = [h.sum() for h in hit] + [nan[0], nan[1]]
+    flts = []
+    f32 = accumulate == torch.float32
+    if f32:       # the reference's own reductions: float32 means (evaluate_mrr / hits_at_k to the bit on one device)
+        flts += [h.float().mean().double() if p else torch.full((), float("nan"), dtype=torch.float64, device=pos.device)
+                 for h in hit]
+    if mrr:
+        if f32:
+            flts.append((1.0 / rank32).mean().double())
+        else:
+            rank64 = 0.5 * (ge.to(torch.int64) + gt).to(torch.float64) + 1.0   # exact: half-integers below 2^32
+            flts.append((1.0 / rank64).sum())
+    m_all = 0
+    if auc:
+        if per_row:   # over the flattened negatives: every positive against all P * K of them
+            if rows.numel() > INT32_MAX:
+                raise ValueError("AUC / AP over [P, K] negatives need P * K <= 2^31 - 1")
+            sn = sn if sn is not None else sort_negatives(rows)
+            ge_a, gt_a, _ = _counts_shared(pos, sn)
+        else:
+            ge_a, gt_a = ge, gt
+        m_all = sn.numel
+        # twice the AUC numerator, an exact integer: sum_i 2 (M - ge_i) + (ge_i - gt_i)
+        ints.append((2 * m_all - ge_a.to(torch.int64) - gt_a).sum())
+        tp, _, _ = _counts_shared(pos, sort_negatives(pos))          # tp_i = #{positives >= pos_i}
+        den = (tp.to(torch.int64) + ge_a).to(torch.float64)
+        flts.append(torch.where(den > 0, tp.to(torch.float64) / den.clamp_min(1.0), torch.zeros_like(den)).sum())
+    ints = [int(v) for v in torch.stack([torch.as_tensor(v, device=pos.device).to(torch.int64) for v in ints]).tolist()]
+    flts = [float(v) for v in torch.stack(flts).tolist()] if flts else []
+    out = {}
+    nanv = float("nan")
+    for i, k in enumerate(ks):
+        if not per_row and m < k:
+            out[f"Hits@{k}"] = 1.0
+        elif f32:
+            out[f"Hits@{k}"] = flts[i]
+        else:
+            out[f"Hits@{k}"] = ints[i] / p if p else nanv
+    j = len(ks) if f32 else 0
+    if mrr:
+        out["MRR"] = (flts[j] if f32 else (flts[j] / p if p else nanv))
+        j += 1
+    if auc:
+        num2 = ints[len(ks) + 2]
+        out["AUC"] = num2 / (2 * p * m_all) if p and m_all else nanv
+        out["AP"] = flts[j] / p if p else nanv
+    out["nan_pos"], out["nan_neg"] = ints[len(ks)], ints[len(ks) + 1]
+    return out
+
+
+def link_metrics(pos, neg, k_list=(20, 50, 100), mrr: bool = True, auc: bool = True,
+                 accumulate: torch.dtype = torch.float64) -> dict:
+    """Ranking metrics of positives against negatives from the two count vectors of ``rank_counts``.
+
+    ``neg`` 1-D or a ``SortedNegatives`` (one shared set, the OGB layout): ``Hits@K = mean(ge < K)``, which is
+    ``mean(pos > K-th largest negative)`` and 1.0 when M < K (``hits_at_k``).  ``neg`` [P, K] (HeaRT / citation2):
+    ``Hits@K = mean(rank <= K)`` (``evaluate_mrr``).  ``MRR = mean(1 / rank)``, rank = 0.5 (ge + gt) + 1.
+    ``AUC = sum_i ((M - ge_i) + 0.5 (ge_i - gt_i)) / (P M)`` from an exact int64 numerator, and
+    ``AP = mean_i tp_i / (tp_i + ge_i)`` with tp_i = #{positives >= pos_i}: sklearn's ``roc_auc_score`` and
+    ``average_precision_score`` on the concatenated labels (``evaluate_auc``, evaluation.py:93-104, unrounded); for
+    [P, K] they are taken over the flattened negatives.  ``nan_pos`` / ``nan_neg`` count the NaN scores seen (an
+    overflowed selection batch scores NaN): a NaN negative ranks below everything, a NaN positive has rank 1 and
+    contributes 0 to AP.  ``accumulate``: float64 (default) sums counts as integers and reciprocal ranks in fp64;
+    float32 takes the float32 means the reference and ``ranking_metrics`` / ``hits_at_k`` take, to the bit."""
+    ks = _check_ks(k_list)
+    pos, rows, sn = _prepare(pos, neg)
+    return _link_metrics(pos, rows, sn, ks, mrr, auc, accumulate)
+
+
+def split_metrics(pos_train, pos_valid, neg_valid, pos_test, neg_test, k_list=(100,), layout: str = "shared",
+                  mrr: bool = True, auc: bool = True) -> dict:
+    """``get_metric_score`` / ``get_metric_score_citation2`` (evaluation.py:108-148):
+    ``{"Hits@K": (train, valid, test), "MRR": (...), "AUC": (...), "AP": (...), "nan_pos": (...), "nan_neg": (...)}``.
+    Train positives are ranked against the VALID negatives, as the reference does.  ``layout="shared"``: the negatives
+    of a split are one set (flattened), sorted once for the train and the valid positives.  ``layout="rows"``:
+    ``neg_*`` [P, K], each positive against its own row (the train positives against the rows of the valid negatives,
+    so there must be as many of them)."""
+    if layout not in ("shared", "rows"):
+        raise ValueError("layout must be 'shared' or 'rows'")
+    ks = _check_ks(k_list)
+    if layout == "shared":
+        nv = sort_negatives(_scores(neg_valid, "neg_valid").reshape(-1))
+        nt = sort_negatives(_scores(neg_test, "neg_test").reshape(-1))
+        parts = [_link_metrics(*_prepare(p, n), ks, mrr, auc, torch.float64)
+                 for p, n in ((pos_train, nv), (pos_valid, nv), (pos_test, nt))]
+    else:
+        parts = []
+        flat = {}
+        for p, n in ((pos_train, neg_valid), (pos_valid, neg_valid), (pos_test, neg_test)):
+            pos, rows, _ = _prepare(p, n)
+            if rows is None:
+                raise ValueError("layout='rows' needs [P, K] negatives")
+            if auc and id(n) not in flat:       # the flattened negatives of a split are sorted once as well
+                flat[id(n)] = sort_negatives(rows)
+            parts.append(_link_metrics(pos, rows, flat.get(id(n)), ks, mrr, auc, torch.float64))
+    return {key: tuple(part[key] for part in parts) for key in parts[0]}
+
+
+@torch.no_grad()
+def evaluate_model(model, score_func, data, batch_size: int = 32768, k_list=(100,), heart: bool = False) -> dict:
+    """The reference's ``test()`` (testing.py:124-161): score ``train_pos_val``, ``valid_pos``, ``test_pos`` and the
+    negatives of ``data`` (one encoder pass per graph; the test split on the test-time graph) and hand the scores,
+    still on the device, to ``split_metrics``.  ``heart``: ``valid_neg`` / ``test_neg`` are [P, K, 2] per-positive
+    negatives (``score_negatives``, the citation2 metrics); otherwise [M, 2] shared ones."""
+    model.eval()
+    score_func.eval()
+    h = model.propagate(test_set=False)
+    h_test = model.propagate(test_set=True)
+    pos_train = score_edges(model, score_func, data["train_pos_val"], batch_size, h=h)
+    pos_valid = score_edges(model, score_func, data["valid_pos"], batch_size, h=h)
+    pos_test = score_edges(model, score_func, data["test_pos"], batch_size, h=h_test, test_set=True)
+    if heart:
+        neg_valid = score_negatives(model, score_func, data["valid_neg"], batch_size, h=h)
+        neg_test = score_negatives(model, score_func, data["test_neg"], batch_size, h=h_test, test_set=True)
+    else:
+        neg_valid = score_edges(model, score_func, data["valid_neg"], batch_size, h=h)
+        neg_test = score_edges(model, score_func, data["test_neg"], batch_size, h=h_test, test_set=True)
+    return split_metrics(pos_train, pos_valid, neg_valid, pos_test, neg_test, k_list=k_list,
+                         layout="rows" if heart else "shared")
+
+
 # Metrics by heuristic bin (src/train/eval.py:44-77 ``test_by_metric``, behind run.py's --bymetric / --percentile,
 # src/run.py:195-196).  The reference's function is unfinished: its predictions are ``...`` placeholders (eval.py:64,66),
 # and it overwrites its bin list with the per-edge counts (``cn_vals = compute_edge_cn(...)``, eval.py:68) before
