@@ -34,7 +34,7 @@ extern "C" {
 #define LPF_ERR_LAUNCH (-3)      /* hipLaunch / runtime error (see lpf_last_hip_error)  */
 #define LPF_ERR_NO_DEVICE (-4)   /* no gfx950 device visible                            */
 
-#define LPF_ABI_VERSION 14
+#define LPF_ABI_VERSION 15
 
 /* GEMM / row-wise epilogue flags */
 #define LPF_FLAG_RELU 1u
@@ -368,6 +368,29 @@ int lpf_pair_softmax_gather_f32(int32_t D, int64_t bs, const int64_t *type_ptr, 
                                 const float *sel_pa, const float *sel_pb, const float *score,
                                 const float *Z, int64_t ldz, const float *pe_tab, const float *pe_stat,
                                 float *G, int64_t ldg, float *alpha_out, int32_t *heavy_scratch, void *stream);
+
+/* Per-pair attribution of the attention (csrc/explain.hip): the same PyG segment softmax over
+ * a pair's CN, 1-hop and >1-hop entries JOINTLY (layers.py:220: max-shift, denominator + 1e-16) as
+ * lpf_pair_softmax_gather_f32, reduced to what explains the pair instead of to the weighted sums -- the reference only
+ * hands out (pair position, alpha) per entry (layers.py:73-75), without node ids or types.  Input: the layout of
+ * lpf_select_export (type_ptr int64[3][bs+1] relative per type, sel_* type-major sorted by (pair, node)) and `score`
+ * of lpf_pair_scores_f32.  Entry counts are read from type_ptr on the device; max_entries is the capacity of sel_*,
+ * score and all_* (nothing is read or written past it).  Per pair p:
+ *   mass     float[bs][3]   sum of alpha per type (CN, 1-hop, >1-hop); an empty pair: 0
+ *   entropy  float[bs]      -sum alpha ln alpha in nats, terms with alpha = 0 contributing 0; an empty pair: 0
+ *   top_*    [bs][top], 1 <= top <= 32: the entries with the largest alpha, best first, ties to the smaller node id, a
+ *            NaN alpha last: top_node int64 (padding -1), top_w float (0), top_type int8 1 = CN, 2 = 1-hop, 3 = >1-hop
+ *            (0), top_pa / top_pb float (0) the PPR values the positional encoding saw (link_transformer.py:182-211)
+ *   all_*    optional (all_ptr NULL to skip) pair-major full list: all_ptr int64[bs+1] = the sum of the three type
+ *            pointers, all_node int64 / all_type int8 / all_w float [max_entries]: a pair's entries in CN, 1-hop,
+ *            >1-hop order, each sorted by node
+ * heavy_scratch: int32[bs+1] (list of the pairs with many entries, taken by a whole workgroup in a second launch).
+ * Sums are accumulated in fp64 and rounded once; no float atomics: results do not depend on the launch shape. */
+int lpf_pair_explain_f32(int64_t bs, const int64_t *type_ptr, const int32_t *sel_node, const float *sel_pa,
+                         const float *sel_pb, const float *score, int64_t max_entries, int32_t top, float *mass,
+                         float *entropy, int64_t *top_node, float *top_w, int8_t *top_type, float *top_pa,
+                         float *top_pb, int64_t *all_ptr, int64_t *all_node, int8_t *all_type, float *all_w,
+                         int32_t *heavy_scratch, void *stream);
 
 /* Fused dense chain (one launch):  y = L2( act( LN( L1(x) + addend ) ) )  on the fp32 matrix cores, hidden activations
  * never leaving registers.  Replaces Linear -> LayerNorm -> ReLU -> Linear chains of other_models.py:125-138 (MLP),

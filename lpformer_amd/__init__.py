@@ -9,11 +9,14 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
                                         evaluate_model: ranks, Hits@K, MRR, AUC, AP from device rank-count kernels
     pair_heuristics                     CN / Adamic-Adar / Resource Allocation (+ PPR, feature cosine) of pairs
     recommend                           top-K new links per source node (device candidates, scoring, top-K)
+    explain, explain_from_scores        per-pair attention attribution: top nodes, mass per type, entropy (device
+                                        segmented reduction); pairs_of (a recommend result's pairs), attention_profile
     heart_negatives, twohop_rows        HeaRT-style hard negatives [P, K, 2] made on the device; rows of A diag(w) A
     update_ppr, update_data, update_graph   graph edits with an exact incremental PPR refresh (ppr_affected_sources)
     graph, data                         CSR containers and the data-dict builder
 """
 from . import evaluate, graph, mask_delta, readers  # noqa: F401
+from .explain import Explanation, attention_profile, explain, explain_from_scores, pairs_of  # noqa: F401
 from .graph import RemovedEdges  # noqa: F401
 from .graph_update import ppr_affected_sources, update_data, update_graph, update_ppr  # noqa: F401
 from .hard_negatives import HardNegatives, heart_negatives, twohop_rows  # noqa: F401
@@ -27,4 +30,5 @@ from .recommend import Recommendations, recommend  # noqa: F401
 __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_ppr_gpu", "get_ppr",
            "load_or_calc_ppr", "ppr_coo", "graph", "evaluate", "GraphedScorer", "PlannedScorer", "RemovedEdges",
            "pair_heuristics", "recommend", "Recommendations", "heart_negatives", "twohop_rows",
-           "HardNegatives", "ppr_affected_sources", "update_ppr", "update_data", "update_graph"]
+           "HardNegatives", "ppr_affected_sources", "update_ppr", "update_data", "update_graph", "explain", "explain_from_scores",
+           "pairs_of", "attention_profile", "Explanation"]

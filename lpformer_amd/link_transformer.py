@@ -1874,6 +1874,31 @@ class LinkTransformer(nn.Module):
                     "lpf_pair_attention_fused_f32")
         return ws, part, bnd, units_cap
 
+    def _pair_scores(self, batch, x_node, test_set, adj_mask):
+        """Front part of the module-by-module attention, shared with ``lpformer_amd.explain``: node keys and pair queries,
+        the selection in the reference layout (``_select``: reads its status back) and ``lpf_pair_scores_f32``.  Returns
+        (selection dict, score [>= cap] -- a workspace of the current stream --, z, folded tables).  Call under
+        ``torch.no_grad()`` with the model's device current."""
+        lib, st, d = _lib.hip(), _stream(self.device), self.dim
+        bs = batch.shape[1]
+        w = self._fold()
+        z = self._node_keys(x_node, w)
+        side = self._fork()
+        with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(self.device)):
+            q = self._pair_q(batch, x_node, w)
+
+        s = self._select(batch, test_set, adj_mask)
+        if side is not None:
+            _lib.stream_wait(torch.cuda.current_stream(self.device), side)  # q (and the elementwise branch) are done
+        score = self._workspace("score", s["cap"], torch.float32, st)
+        with KernelTimer.span("pair_scores"):
+            check(lib.lpf_pair_scores_f32(d, ptr(s["type_ptr"]), bs, ptr(s["sel_pair"]), ptr(s["sel_node"]),
+                                          ptr(s["sel_pa"]), ptr(s["sel_pb"]), ptr(z), z.stride(0), ptr(q),
+                                          q.stride(0), ptr(w["pe_tab"]), ptr(w["pe_stat"]), ptr(w["wfold_packed"]),
+                                          ptr(w["bfold"]), ptr(w["att"]), ptr(score), s["cap"], st),
+                  "lpf_pair_scores_f32")
+        return s, score, z, w
+
     def _pair_attention(self, batch, x_node, test_set, adj_mask, return_weights, stop_after_gather=False):
         """Selection -> PE + attention (+ post-norm) -> count features.  Returns (feats [BS, ld] = [attention output |
         counts | pad], att_weights or None, unchecked); the caller applies ``pairwise_lin`` (or its folded first
@@ -1907,22 +1932,7 @@ class LinkTransformer(nn.Module):
                         ptr(ws.ctl), ptr(feats), ld, st), "lpf_pair_attention_merge_f32")
                 self._last_att = feats[:, :d]
                 return feats, None, True   # (unchecked: calc_pairwise reads the status back after queueing its own work)
-            w = self._fold()
-            z = self._node_keys(x_node, w)
-            side = self._fork()
-            with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(self.device)):
-                q = self._pair_q(batch, x_node, w)
-
-            s = self._select(batch, test_set, adj_mask)
-            if side is not None:
-                _lib.stream_wait(torch.cuda.current_stream(self.device), side)  # q (and the elementwise branch) are done
-            score = self._workspace("score", s["cap"], torch.float32, st)
-            with KernelTimer.span("pair_scores"):
-                check(lib.lpf_pair_scores_f32(d, ptr(s["type_ptr"]), bs, ptr(s["sel_pair"]), ptr(s["sel_node"]),
-                                              ptr(s["sel_pa"]), ptr(s["sel_pb"]), ptr(z), z.stride(0), ptr(q),
-                                              q.stride(0), ptr(w["pe_tab"]), ptr(w["pe_stat"]), ptr(w["wfold_packed"]),
-                                              ptr(w["bfold"]), ptr(w["att"]), ptr(score), s["cap"], st),
-                      "lpf_pair_scores_f32")
+            s, score, z, w = self._pair_scores(batch, x_node, test_set, adj_mask)
             ldg = 4 * d + 4
             g = torch.empty(bs, ldg, dtype=torch.float32, device=self.device)
             alpha = torch.empty(s["cap"], dtype=torch.float32, device=self.device) if return_weights else None
