@@ -34,7 +34,7 @@ extern "C" {
 #define LPF_ERR_LAUNCH (-3)      /* hipLaunch / runtime error (see lpf_last_hip_error)  */
 #define LPF_ERR_NO_DEVICE (-4)   /* no gfx950 device visible                            */
 
-#define LPF_ABI_VERSION 15
+#define LPF_ABI_VERSION 16
 
 /* GEMM / row-wise epilogue flags */
 #define LPF_FLAG_RELU 1u
@@ -891,6 +891,41 @@ int64_t lpf_rank_shared_workspace_bytes(int64_t P, int64_t M);
 int lpf_rank_shared_f32(int64_t P, const float *pos, int64_t M, const float *neg, uint32_t *sorted_keys,
                         void *workspace, int64_t workspace_bytes, int32_t *ge, int32_t *gt, int64_t *nan_counts,
                         void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Threshold profile (thresh_profile.hip): the nodes of each type every pair would select at each threshold of a grid
+ * -- what thresh_cn / thresh_1hop / thresh_non1hop (src/models/link_transformer.py:241-250, 478) cost and see, for the
+ * whole grid the reference searches (src/run.py:199-201) in one pass over the unfiltered graphs.
+ * ---------------------------------------------------------------------------------------------- */
+/* Largest number of thresholds of one call. */
+#define LPF_THRESH_MAX_T 32
+/* Pairs whose walked length exceeds this go to the workgroup-per-pair kernel (split_threshold < 0 selects it). */
+#define LPF_THRESH_SPLIT_DEFAULT 512
+/* For pair p = (a, b) = (pairs[p], pairs[pairs_ld + p]), the binary typing adjacency adj_* and the raw PPR matrix ppr_*
+ * (CSRs of the same n nodes with sorted, unique columns; fp32 values, 0 where nothing is stored), candidate v has
+ *   type 0 (common neighbour)  v in N(a) & N(b):                        ra = rt2(P[a,v]), rb = rt2(P[b,v])
+ *   type 1 (one-hop)           v in exactly one of N(a), N(b):          ra = rt1(P[a,v]), rb = rt1(P[b,v])
+ *   type 2 (>1-hop)            v in neither, P[a,v] > 0 and P[b,v] > 0: ra = rt1(P[a,v]), rb = rt1(P[b,v])
+ * with the reference's fp32 round trips rt1(x) = fl(fl(x + 1) - 1), rt2(x) = fl(fl(2 x + 2) - 2) / 2, and
+ *   count[p][t][j] = #{v of type t : ra >= thresholds[j] and rb >= thresholds[j]}
+ * -- the nodes of type t a model with that threshold for the type selects for the pair, bit for bit.  No special case
+ * for v in {a, b} or a == b.  mode_cn != 0 (mask mode "cn"): type 0 uses rt1, types 1 and 2 are empty.  A pair with an
+ * id outside [0, n) counts nothing.
+ * thresholds: HOST array of T values, 1 <= T <= LPF_THRESH_MAX_T, finite, >= 0, strictly ascending (else
+ * LPF_ERR_INVALID, P == 0 included); they travel in the launch arguments.  Every other pointer is device memory.
+ * per_pair int32[P][3][T] receives count (NULL: not written).  total int64[3][T] += sum over p of count,
+ * max_per_pair int32[3][T] = max(itself, max over p), nonempty int64[3][T] += #{p : count > 0}: accumulated, so a caller
+ * may chunk the pairs; it zeroes them first.
+ * The pair's walks are N(a), N(b) minus N(a) and the shorter of the two PPR rows, deg(a) + deg(b) + min(|P_a|, |P_b|)
+ * slots with three binary searches each: up to split_threshold slots one wavefront takes the pair, longer ones get a
+ * 256-thread workgroup each (a second kernel over a list the first fills; 0 sends every non-empty pair there).
+ * Counts come from ballots and integer LDS counters, the three reductions from integer atomics: the result is a pure
+ * function of the input, whatever the split.  scratch: int32[P + 1].  P < 2^31 - 1. */
+int lpf_threshold_profile(int64_t P, int64_t n, const int64_t *pairs, int64_t pairs_ld, const int64_t *adj_rowptr,
+                          const int32_t *adj_col, const int64_t *ppr_rowptr, const int32_t *ppr_col,
+                          const float *ppr_val, int32_t T, const float *thresholds, int32_t mode_cn,
+                          int32_t split_threshold, int32_t *scratch, int32_t *per_pair, int64_t *total,
+                          int32_t *max_per_pair, int64_t *nonempty, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training step of the pair stage (pair_train.hip): the forward of get_pos_encodings

@@ -11,6 +11,8 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
     recommend                           top-K new links per source node (device candidates, scoring, top-K)
     explain, explain_from_scores        per-pair attention attribution: top nodes, mass per type, entropy (device
                                         segmented reduction); pairs_of (a recommend result's pairs), attention_profile
+    threshold_profile, suggest_thresholds   selected-node counts per pair, type and PPR threshold for a whole grid of
+                                        thresholds in one device pass; the grid triple that fits an entry budget
     heart_negatives, twohop_rows        HeaRT-style hard negatives [P, K, 2] made on the device; rows of A diag(w) A
     update_ppr, update_data, update_graph   graph edits with an exact incremental PPR refresh (ppr_affected_sources)
     graph, data                         CSR containers and the data-dict builder
@@ -26,9 +28,10 @@ from .link_transformer import MLP, LinkTransformer, mlp_score  # noqa: F401
 from .ppr import calc_ppr, calc_ppr_gpu, get_ppr, load_or_calc_ppr, ppr_coo  # noqa: F401
 from .pyg_api import LPFormer  # noqa: F401
 from .recommend import Recommendations, recommend  # noqa: F401
+from .threshold_profile import ThresholdProfile, suggest_thresholds, threshold_profile  # noqa: F401
 
 __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_ppr_gpu", "get_ppr",
            "load_or_calc_ppr", "ppr_coo", "graph", "evaluate", "GraphedScorer", "PlannedScorer", "RemovedEdges",
            "pair_heuristics", "recommend", "Recommendations", "heart_negatives", "twohop_rows",
            "HardNegatives", "ppr_affected_sources", "update_ppr", "update_data", "update_graph", "explain", "explain_from_scores",
-           "pairs_of", "attention_profile", "Explanation"]
+           "pairs_of", "attention_profile", "Explanation", "threshold_profile", "suggest_thresholds", "ThresholdProfile"]

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "liblpformer_hip.so")
 HOST_LIB_PATH = os.path.join(_HERE, "liblpformer_host.so")
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 FLAG_RELU = 1
 SELECT_ERR_NODE_RANGE, SELECT_ERR_ITEM_CAP, SELECT_ERR_ENTRY_CAP = 1, 2, 4
 ROWS_PERM_LB_WORDS = 1025      # LPF_ROWS_PERM_LB_WORDS (include/lpformer_hip.h)
@@ -106,6 +106,7 @@ HIP_PROTOTYPES = {
     "lpf_pool_fill": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp,
                       vp],
     "lpf_rank_interleave": [i64, i64, vp, i32, i32, vp, vp, vp, vp, vp, u64, vp, vp, vp],
+    "lpf_threshold_profile": [i64, i64, vp, i64, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp],
     "lpf_rank_rows_f32": [i64, i64, vp, vp, i64, vp, vp, vp, vp],
     "lpf_rank_shared_workspace_bytes": [i64, i64],
     "lpf_rank_shared_f32": [i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp],
