@@ -928,6 +928,26 @@ int lpf_threshold_profile(int64_t P, int64_t n, const int64_t *pairs, int64_t pa
                           int32_t *max_per_pair, int64_t *nonempty, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Batch cover (batch_cover.hip): the undirected edges a batch of train_pos ROWS removes from the typing adjacency.
+ * The reference's loop drops the batch's rows and builds a symmetric adjacency from the rest
+ * (src/train/train_model.py:40-45: adjmask[perm] = 0; SparseTensor.from_edge_index(train_pos[adjmask]).to_symmetric()):
+ * an edge {u, v} is absent from it iff EVERY row that holds it, as (u, v) or (v, u), is in the batch.
+ * ---------------------------------------------------------------------------------------------- */
+/* train_pos int64[E][2]; gid int32[E] = group of row e (rows with the same {min, max} share a group), mult int32[G] =
+ * rows per group; cnt int32[G] scratch, all zero on entry and all zero again when the call's work has run.
+ * perm int64[B]: DISTINCT row ids, a slice of a permutation (a row named twice is counted twice and its group, seeing
+ * more rows than it has, is held back).  out int64[2][B]: position i receives (min, max) of row perm[i] iff all
+ * mult[g] rows of its group g are in perm, else (-1, -1) -- a group with several rows in the batch is emitted at each
+ * of them; the shape is fixed and nothing is read back.
+ * stats int32[4] is ADDED to, never reset: [0] positions emitted, [1] positions held back (a twin row is outside the
+ * batch), [2] positions skipped -- perm[i] outside [0, E) (or a gid outside [0, G)): they write (-1, -1) and no other
+ * memory is touched for them --, [3] spare.
+ * Three launches in stream order (count with integer atomics, emit, reset with plain stores): emit sees the counts of
+ * the whole batch.  Integers only: the result is a pure function of the input.  B, E < 2^31 - 1; B == 0 does nothing. */
+int lpf_batch_cover(const int32_t *gid, const int32_t *mult, const int64_t *train_pos, int64_t E, int64_t G,
+                    const int64_t *perm, int64_t B, int32_t *cnt, int64_t *out, int32_t *stats, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training step of the pair stage (pair_train.hip): the forward of get_pos_encodings
  * (link_transformer.py:182-211) and LinkAttention.message + PyG softmax + scatter-sum (layers.py:193-224) with the
  * state a backward pass needs, and the gradients torch autograd derives from them (the reference's training step,

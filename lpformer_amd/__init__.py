@@ -15,9 +15,12 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
                                         thresholds in one device pass; the grid triple that fits an entry budget
     heart_negatives, twohop_rows        HeaRT-style hard negatives [P, K, 2] made on the device; rows of A diag(w) A
     update_ppr, update_data, update_graph   graph edits with an exact incremental PPR refresh (ppr_affected_sources)
+    TrainEdges, train_epoch, fit        the training epoch: the reference's per-batch edge mask made exactly on the
+                                        device (repeated pairs included), the loop, and epochs with early stopping
     graph, data                         CSR containers and the data-dict builder
 """
 from . import evaluate, graph, mask_delta, readers  # noqa: F401
+from .epoch import TrainEdges, fit, train_epoch  # noqa: F401
 from .explain import Explanation, attention_profile, explain, explain_from_scores, pairs_of  # noqa: F401
 from .graph import RemovedEdges  # noqa: F401
 from .graph_update import ppr_affected_sources, update_data, update_graph, update_ppr  # noqa: F401
@@ -34,4 +37,5 @@ __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_
            "load_or_calc_ppr", "ppr_coo", "graph", "evaluate", "GraphedScorer", "PlannedScorer", "RemovedEdges",
            "pair_heuristics", "recommend", "Recommendations", "heart_negatives", "twohop_rows",
            "HardNegatives", "ppr_affected_sources", "update_ppr", "update_data", "update_graph", "explain", "explain_from_scores",
-           "pairs_of", "attention_profile", "Explanation", "threshold_profile", "suggest_thresholds", "ThresholdProfile"]
+           "pairs_of", "attention_profile", "Explanation", "threshold_profile", "suggest_thresholds", "ThresholdProfile",
+           "TrainEdges", "train_epoch", "fit"]

@@ -107,6 +107,7 @@ HIP_PROTOTYPES = {
                       vp],
     "lpf_rank_interleave": [i64, i64, vp, i32, i32, vp, vp, vp, vp, vp, u64, vp, vp, vp],
     "lpf_threshold_profile": [i64, i64, vp, i64, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp],
+    "lpf_batch_cover": [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp],
     "lpf_rank_rows_f32": [i64, i64, vp, vp, i64, vp, vp, vp, vp],
     "lpf_rank_shared_workspace_bytes": [i64, i64],
     "lpf_rank_shared_f32": [i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp],

@@ -197,7 +197,14 @@ class RemovedEdges:
     ``model(edges, adj_mask=masked_adj)`` accepts that tensor as it is -- the difference to the resident adjacency is then
     found on the device --; a loop that knows which edges it removed can say so directly,
     ``model(edges, adj_mask=lpformer_amd.RemovedEdges(edges))``, and skip building the tensor.
-    ``edges``: [2, K] node ids (either direction; edges the adjacency does not hold are ignored)."""
+    ``edges``: [2, K] node ids (either direction; edges the adjacency does not hold and ids outside [0, n) are ignored).
+
+    Precondition for parity with the reference: every named edge is removed UNCONDITIONALLY.  The reference drops the
+    batch's ROWS of ``train_pos``, so a pair that another row outside the batch also holds -- ogbl-collab's repeated
+    pairs, or (u, v) next to (v, u) -- stays in its masked adjacency.  ``RemovedEdges(train_pos[perm].t())`` is the
+    reference's mask only when every row of ``train_pos`` is a distinct undirected pair; for lists with repeated pairs
+    ``lpformer_amd.TrainEdges(train_pos, n).mask(perm)`` (what ``lpformer_amd.train_epoch`` passes) names exactly the
+    edges whose rows are ALL in the batch."""
 
     def __init__(self, edges):
         self.edges = edges
