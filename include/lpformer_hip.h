@@ -948,6 +948,45 @@ int lpf_batch_cover(const int32_t *gid, const int32_t *mult, const int64_t *trai
                     const int64_t *perm, int64_t B, int32_t *cnt, int64_t *out, int32_t *stats, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Pair distance (pair_bfs.hip): shortest-path hops between the endpoints of candidate pairs on the typing adjacency --
+ * the global structural heuristic next to CN / AA / RA (the "shortest path" baseline of HeaRT / OGB comparisons).  The
+ * reference has no such code.
+ * ---------------------------------------------------------------------------------------------- */
+/* The front kernel settles distance 2 itself when the pair's shorter row holds at most this many entries
+ * (split_threshold < 0 selects it); longer rows go to the search kernel.  Chosen from the threshold sweep of
+ * tools/pair_distance_time.py (profiles/pair_distance_timing.json: MI355X, collab-like graph, 32,768 pairs, 569
+ * workgroups), whole-call ms at thresholds 0 / 8 / 32 / 128 / 512:
+ *   held-out positives  unlimited 1.420 / 1.428 / 1.448 / 1.533 / 1.694   max_dist 3 1.113 / 1.123 / 1.144 / 1.227 / 1.386
+ *   uniform random      unlimited 1.466 / 1.483 / 1.497 / 1.529 / 1.530   max_dist 3 0.916 / 0.932 / 0.944 / 0.975 / 0.975
+ * Time only grows with the threshold: a lane that walks a long row alone holds its wave back, and the search
+ * workgroups take a distance-2 pair in their stride.  8 stays within 2 % of the fastest entry (0) in all four columns
+ * -- no more than two 5-repetition means differ by -- where 32, the value LPF_HEUR_SPLIT_DEFAULT has, costs 2-3 % and
+ * 128 and above 4-19 %; unlike 0 it keeps the pairs of two short rows, a handful of probes each, off the list. */
+#define LPF_BFS_SPLIT_DEFAULT 8
+/* Bytes of workspace for n_groups resident workgroups: per group n 32-bit stamp words and a visit list of n + 2
+ * int32: n_groups * (8 n + 8). */
+int64_t lpf_pair_bfs_workspace_bytes(int64_t n, int64_t n_groups);
+/* For pair p = (a, b) = (pairs[p], pairs[pairs_ld + p]) of a CSR with sorted, unique columns and a SYMMETRIC pattern
+ * (values ignored; a non-symmetric pattern is outside the contract), dist[p] is, by the first rule that applies:
+ *   0 when a == b (whatever the options);  -1 when an id lies outside [0, n);  the number of edges of a shortest a-b
+ *   path;  -1 when there is no path.
+ * flags bit 0 (ignore_direct): the stored entries (a, b) and (b, a) of this pair count as absent, nothing else changes.
+ * max_dist = m > 0: a distance above m reads -1 -- exactly where(exact <= m, exact, -1) --, and the search stops as
+ * soon as that is decided; max_dist <= 0: unlimited.  Stored self-loops change nothing.
+ * A front kernel (one lane per pair) settles a == b, bad ids, endpoints without a usable entry, distance 1 and, for
+ * pairs whose shorter row holds at most split_threshold entries, distance 2; the other pairs are listed and persistent
+ * 256-thread workgroups take them by an atomic ticket, each running a bidirectional level-synchronous BFS with dense
+ * epoch-stamped state over all n nodes (claims by integer compare-and-swap, appends by ballot rank).  The result is a
+ * pure function of (graph, pair, options): not of the pair's position, of (a, b) versus (b, a), of split_threshold, of
+ * n_groups or of timing; two runs are bitwise equal.  Integers only.
+ * scratch: int32[P + 1] (the list; its counter is zeroed here).  workspace: lpf_pair_bfs_workspace_bytes(n, n_groups)
+ * bytes, 16-byte aligned, 1 <= n_groups <= 65535; its stamps are zeroed here, once per call.  P < 2^31 - 1,
+ * n < 2^31 - 3.  P == 0 returns LPF_OK without a launch. */
+int lpf_pair_bfs(int64_t P, int64_t n, const int64_t *pairs, int64_t pairs_ld, const int64_t *rowptr,
+                 const int32_t *col, int32_t max_dist, int32_t flags, int32_t split_threshold, int32_t *scratch,
+                 void *workspace, int64_t n_groups, int32_t *dist, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training step of the pair stage (pair_train.hip): the forward of get_pos_encodings
  * (link_transformer.py:182-211) and LinkAttention.message + PyG softmax + scatter-sum (layers.py:193-224) with the
  * state a backward pass needs, and the gradients torch autograd derives from them (the reference's training step,

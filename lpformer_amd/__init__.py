@@ -8,6 +8,8 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
                                         rank_counts / ranks / sample_hits / link_metrics / split_metrics /
                                         evaluate_model: ranks, Hits@K, MRR, AUC, AP from device rank-count kernels
     pair_heuristics                     CN / Adamic-Adar / Resource Allocation (+ PPR, feature cosine) of pairs
+    pair_distance, DIST_BINS            shortest-path hops per pair (device bidirectional BFS) and its bins for
+                                        metrics_by_bin / attention_profile
     recommend                           top-K new links per source node (device candidates, scoring, top-K)
     explain, explain_from_scores        per-pair attention attribution: top nodes, mass per type, entropy (device
                                         segmented reduction); pairs_of (a recommend result's pairs), attention_profile
@@ -20,6 +22,7 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
     graph, data                         CSR containers and the data-dict builder
 """
 from . import evaluate, graph, mask_delta, readers  # noqa: F401
+from .distance import DIST_BINS, pair_distance  # noqa: F401
 from .epoch import TrainEdges, fit, train_epoch  # noqa: F401
 from .explain import Explanation, attention_profile, explain, explain_from_scores, pairs_of  # noqa: F401
 from .graph import RemovedEdges  # noqa: F401
@@ -38,4 +41,4 @@ __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_
            "pair_heuristics", "recommend", "Recommendations", "heart_negatives", "twohop_rows",
            "HardNegatives", "ppr_affected_sources", "update_ppr", "update_data", "update_graph", "explain", "explain_from_scores",
            "pairs_of", "attention_profile", "Explanation", "threshold_profile", "suggest_thresholds", "ThresholdProfile",
-           "TrainEdges", "train_epoch", "fit"]
+           "TrainEdges", "train_epoch", "fit", "pair_distance", "DIST_BINS"]

@@ -482,7 +482,10 @@ def metrics_by_bin(pos: torch.Tensor, neg: torch.Tensor, values: torch.Tensor, b
     pos [P] scores of the positives, values [P] the value each is binned by, bins a sequence of half-open [lo, hi).
     ``neg`` 1-D (the OGB Hits layout): every bin's positives against ALL negatives, ``Hits@K`` for K in ``k_list``
     (``hits_at_k``).  ``neg`` [P, K] (HeaRT / citation2: each positive's own negatives): ``ranking_metrics`` over the
-    rows of the bin.  Returns one dict per bin: ``bin`` (lo, hi), ``count`` and the metrics -- NaN for an empty bin."""
+    rows of the bin.  Returns one dict per bin: ``bin`` (lo, hi), ``count`` and the metrics -- NaN for an empty bin.
+
+    Any per-positive value works, e.g. the hop distance of the endpoints:
+    ``metrics_by_bin(pos, neg, pair_distance(model, pos_edges), bins=distance.DIST_BINS)``."""
     pos = torch.as_tensor(pos).reshape(-1)
     neg = torch.as_tensor(neg)
     values = torch.as_tensor(values).reshape(-1).to(pos.device)
