@@ -48,6 +48,14 @@ int lpf_blocks_per_cu(LpfPerDevice &cache, const void *kern, int threads, size_t
 
 static inline bool lpf_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// zero the counter in front of a long list (scratch[0]) on stream s
+static inline int lpf_reset_counter(int32_t *scratch, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(scratch, 0, sizeof(int32_t), s);
+    if (e == hipSuccess) return LPF_OK;
+    lpf_set_hip_error(e);
+    return LPF_ERR_LAUNCH;
+}
+
 __device__ __forceinline__ int lpf_lane() { return (int)(threadIdx.x & 63); }
 
 // xor-butterfly reductions over the low `WIDTH` lanes of each aligned group (WIDTH power of two <= 64)
@@ -71,6 +79,23 @@ __device__ __forceinline__ int64_t lpf_lower_bound(const int32_t *__restrict__ a
         if (a[mid] < key) lo = mid + 1; else hi = mid;
     }
     return lo;
+}
+// whether the sorted row col[lo, hi) holds key
+__device__ __forceinline__ bool lpf_sorted_has(const int32_t *__restrict__ col, int64_t lo, int64_t hi, int32_t key) {
+    const int64_t i = lpf_lower_bound(col, lo, hi, key);
+    return i < hi && col[i] == key;
+}
+
+// The flagged lanes of a wave append `item` to list[1 ..]; list[0] counts the entries: one ticket per wave, its lanes
+// take consecutive slots.  Call it wave-uniformly.
+__device__ __forceinline__ void lpf_wave_list_push(int32_t *__restrict__ list, bool flag, int32_t item) {
+    const uint64_t m = __ballot(flag);
+    if (!m) return;
+    const int lane = lpf_lane();
+    int base = 0;
+    if (lane == 0) base = atomicAdd(&list[0], __popcll(m));
+    base = __shfl(base, 0);
+    if (flag) list[1 + base + __popcll(m & ((1ull << lane) - 1ull))] = item;
 }
 
 // fp32 <-> bf16 bits (round to nearest even; NaN stays NaN)

@@ -65,13 +65,7 @@ struct BfsArgs {
     int32_t *dist;
 };
 
-__device__ __forceinline__ bool bfs_has(const int32_t *__restrict__ col, int64_t lo, int64_t hi, int64_t key) {
-    const int64_t i = lpf_lower_bound(col, lo, hi, (int32_t)key);
-    return i < hi && col[i] == (int32_t)key;
-}
-
 __global__ __launch_bounds__(BFS_BLOCK) void bfs_front_kernel(BfsArgs A) {
-    const int lane = lpf_lane();
     const int64_t p = (int64_t)blockIdx.x * BFS_BLOCK + threadIdx.x;
     const int32_t *__restrict__ col = A.col;
     int32_t d = -1;
@@ -82,7 +76,7 @@ __global__ __launch_bounds__(BFS_BLOCK) void bfs_front_kernel(BfsArgs A) {
             d = 0;
         } else if ((uint64_t)a < (uint64_t)A.n && (uint64_t)b < (uint64_t)A.n) {
             const int64_t a0 = A.rowptr[a], a1 = A.rowptr[a + 1], b0 = A.rowptr[b], b1 = A.rowptr[b + 1];
-            const bool e_ab = bfs_has(col, a0, a1, b), e_ba = bfs_has(col, b0, b1, a);
+            const bool e_ab = lpf_sorted_has(col, a0, a1, (int32_t)b), e_ba = lpf_sorted_has(col, b0, b1, (int32_t)a);
             const int64_t da = a1 - a0 - (A.ignore_direct && e_ab ? 1 : 0);
             const int64_t db = b1 - b0 - (A.ignore_direct && e_ba ? 1 : 0);
             if (da <= 0 || db <= 0) {
@@ -100,7 +94,7 @@ __global__ __launch_bounds__(BFS_BLOCK) void bfs_front_kernel(BfsArgs A) {
                     bool hit = false;
                     for (int64_t j = w0; j < w1 && !hit; ++j) {
                         const int32_t w = col[j];     // (a column equal to a or b is a self-loop or the direct entry)
-                        hit = w != (int32_t)a && w != (int32_t)b && bfs_has(col, q0, q1, w);
+                        hit = w != (int32_t)a && w != (int32_t)b && lpf_sorted_has(col, q0, q1, w);
                     }
                     if (hit) d = 2;
                     else if (A.max_dist == 2) d = -1;
@@ -109,13 +103,7 @@ __global__ __launch_bounds__(BFS_BLOCK) void bfs_front_kernel(BfsArgs A) {
             }
         }
     }
-    const uint64_t lm = __ballot(listed);
-    if (lm) {                                     // one ticket per wave, the lanes take consecutive list slots
-        int base = 0;
-        if (lane == 0) base = atomicAdd(&A.list[0], __popcll(lm));
-        base = __shfl(base, 0);
-        if (listed) A.list[1 + base + __popcll(lm & ((1ull << lane) - 1ull))] = (int32_t)p;
-    }
+    lpf_wave_list_push(A.list, listed, (int32_t)p);
     if (p < A.P && !listed) A.dist[p] = d;
 }
 

@@ -65,14 +65,7 @@ __global__ __launch_bounds__(HEUR_BLOCK) void heur_short_kernel(
     if (live) r = pair_rows(pairs[p], pairs[ld + p], n, rowptr);
     const bool is_long = live && r.len > thr;
 
-    // long pairs: one ticket per wave, the lanes take consecutive list slots
-    const uint64_t lm = __ballot(is_long);
-    if (lm) {
-        int base = 0;
-        if (lane == 0) base = atomicAdd(&long_list[0], __popcll(lm));
-        base = __shfl(base, 0);
-        if (is_long) long_list[1 + base + __popcll(lm & ((1ull << lane) - 1ull))] = (int32_t)p;
-    }
+    lpf_wave_list_push(long_list, is_long, (int32_t)p);
 
     // short pairs: flatten the walked rows of the wave's pairs into one slot stream (inclusive scan of the lengths)
     const int32_t len = is_long ? 0 : r.len;
@@ -103,8 +96,7 @@ __global__ __launch_bounds__(HEUR_BLOCK) void heur_short_kernel(
         float ta = 0.f, tr = 0.f;
         if (f < total) {
             const int32_t key = col[r0 + j];
-            const int64_t i = lpf_lower_bound(col, q0, q0 + qlen, key);
-            hit = i < q0 + qlen && col[i] == key;
+            hit = lpf_sorted_has(col, q0, q0 + qlen, key);
             if (hit && (uint64_t)key < (uint64_t)n) {   // (a column outside [0, n) would index past the tables)
                 if (aa) ta = w_aa[key];
                 if (ra) tr = w_ra[key];
@@ -200,11 +192,7 @@ extern "C" int lpf_pair_heuristics_f32(int64_t P, int64_t n, const int64_t *pair
     if (!cn && !aa && !ra) return LPF_OK;
     const int32_t thr = split_threshold < 0 ? LPF_HEUR_SPLIT_DEFAULT : split_threshold;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const hipError_t e = hipMemsetAsync(scratch, 0, sizeof(int32_t), s);   // long-pair counter
-    if (e != hipSuccess) {
-        lpf_set_hip_error(e);
-        return LPF_ERR_LAUNCH;
-    }
+    if (lpf_reset_counter(scratch, s) != LPF_OK) return LPF_ERR_LAUNCH;   // long-pair counter
     const int64_t pairs_per_block = (int64_t)HEUR_BLOCK;   // one pair per lane
     hipLaunchKernelGGL(heur_short_kernel, dim3((unsigned)((P + pairs_per_block - 1) / pairs_per_block)),
                        dim3(HEUR_BLOCK), 0, s, P, n, pairs, pairs_ld, rowptr, col, w_aa, w_ra, thr, scratch, cn, aa,

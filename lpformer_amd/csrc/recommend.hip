@@ -58,11 +58,6 @@ struct CandArgs {
     int64_t *pairs;                             // fill pass: [2, P]
 };
 
-__device__ __forceinline__ bool sorted_has(const int32_t *a, int64_t lo, int64_t hi, int32_t key) {
-    const int64_t i = lpf_lower_bound(a, lo, hi, key);
-    return i < hi && a[i] == key;
-}
-
 __device__ __forceinline__ void exc_row(const CandArgs &A, int64_t u, int64_t &e0, int64_t &e1) {
     e0 = e1 = 0;
     if (A.exc_rowptr) {
@@ -113,7 +108,7 @@ __global__ __launch_bounds__(REC_BLOCK) void rec_short_kernel(CandArgs A) {
         bool keep = false;
         if (j < len) {
             keep = inc_keep(A, u, r0 + j, v);
-            if (keep && x1 > x0) keep = !sorted_has(ex, x0, x1, v);
+            if (keep && x1 > x0) keep = !lpf_sorted_has(ex, x0, x1, v);
         }
         const uint64_t m = __ballot(keep);
         if (A.offset && keep) {
@@ -393,11 +388,7 @@ __global__ __launch_bounds__(REC_TOPK_BLOCK) void topk_block_kernel(const int64_
 
 int rec_candidates(const CandArgs &A, void *stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const hipError_t e = hipMemsetAsync(A.long_list, 0, sizeof(int32_t), s);   // long-row counter
-    if (e != hipSuccess) {
-        lpf_set_hip_error(e);
-        return LPF_ERR_LAUNCH;
-    }
+    if (lpf_reset_counter(A.long_list, s) != LPF_OK) return LPF_ERR_LAUNCH;   // long-row counter
     hipLaunchKernelGGL(rec_short_kernel, dim3((unsigned)((A.S + REC_WAVES - 1) / REC_WAVES)), dim3(REC_BLOCK), 0, s,
                        A);
     LPF_CHECK_LAUNCH();
@@ -473,11 +464,7 @@ extern "C" int lpf_segment_topk_f32(int64_t S, const int64_t *seg_ptr, const flo
     LPF_REQUIRE(S > 0 && S < INT32_MAX && k >= 1 && k <= LPF_TOPK_MAX_K && seg_ptr && score && cand && scratch && ids &&
                 scores && counts);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const hipError_t e = hipMemsetAsync(scratch, 0, sizeof(int32_t), s);   // long-segment counter
-    if (e != hipSuccess) {
-        lpf_set_hip_error(e);
-        return LPF_ERR_LAUNCH;
-    }
+    if (lpf_reset_counter(scratch, s) != LPF_OK) return LPF_ERR_LAUNCH;   // long-segment counter
     hipLaunchKernelGGL(topk_wave_kernel, dim3((unsigned)((S + REC_WAVES - 1) / REC_WAVES)), dim3(REC_BLOCK), 0, s, S,
                        seg_ptr, score, cand, k, scratch, ids, scores, counts);
     LPF_CHECK_LAUNCH();

@@ -83,11 +83,6 @@ __device__ __forceinline__ PairWalk pair_walk(const ProfArgs &A, int64_t p) {
 
 __device__ __forceinline__ int64_t walk_len(const PairWalk &w) { return (int64_t)w.w1 + w.w2 + w.w3; }
 
-__device__ __forceinline__ bool row_has(const int32_t *__restrict__ col, int64_t r0, int32_t len, int32_t key) {
-    const int64_t i = lpf_lower_bound(col, r0, r0 + len, key);
-    return i < r0 + len && col[i] == key;
-}
-
 // P[row, key] (0 where nothing is stored); `found` says whether an entry is stored
 __device__ __forceinline__ float row_val(const int32_t *__restrict__ col, const float *__restrict__ val, int64_t r0,
                                          int32_t len, int32_t key, bool &found) {
@@ -104,14 +99,14 @@ __device__ __forceinline__ int slot_type(const ProfArgs &A, const PairWalk &w, i
     bool found;
     if (f < w.w1) {                              // N(a)
         const int32_t v = A.adj_col[w.a0 + f];
-        const bool cn = row_has(A.adj_col, w.b0, w.db, v);
+        const bool cn = lpf_sorted_has(A.adj_col, w.b0, w.b0 + w.db, v);
         if (A.mode_cn && !cn) return -1;
         type = cn ? 0 : 1;
         va = row_val(A.ppr_col, A.ppr_val, w.pa0, w.la, v, found);
         vb = row_val(A.ppr_col, A.ppr_val, w.pb0, w.lb, v, found);
     } else if (f < (int64_t)w.w1 + w.w2) {       // N(b) minus N(a)
         const int32_t v = A.adj_col[w.b0 + (f - w.w1)];
-        if (row_has(A.adj_col, w.a0, w.da, v)) return -1;
+        if (lpf_sorted_has(A.adj_col, w.a0, w.a0 + w.da, v)) return -1;
         type = 1;
         va = row_val(A.ppr_col, A.ppr_val, w.pa0, w.la, v, found);
         vb = row_val(A.ppr_col, A.ppr_val, w.pb0, w.lb, v, found);
@@ -123,7 +118,7 @@ __device__ __forceinline__ int slot_type(const ProfArgs &A, const PairWalk &w, i
         const float ws = A.ppr_val[s0 + i];
         const float wo = row_val(A.ppr_col, A.ppr_val, src_a ? w.pb0 : w.pa0, src_a ? w.lb : w.la, v, found);
         if (!(found && ws > 0.f && wo > 0.f)) return -1;
-        if (row_has(A.adj_col, w.a0, w.da, v) || row_has(A.adj_col, w.b0, w.db, v)) return -1;
+        if (lpf_sorted_has(A.adj_col, w.a0, w.a0 + w.da, v) || lpf_sorted_has(A.adj_col, w.b0, w.b0 + w.db, v)) return -1;
         type = 2;
         va = src_a ? ws : wo;
         vb = src_a ? wo : ws;
@@ -296,11 +291,7 @@ extern "C" int lpf_threshold_profile(int64_t P, int64_t n, const int64_t *pairs,
     A.max_per_pair = max_per_pair;
     for (int j = 0; j < TP_MAX_T; ++j) A.th[j] = j < T ? thresholds[j] : 0.f;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const hipError_t e = hipMemsetAsync(scratch, 0, sizeof(int32_t), s);   // long-pair counter
-    if (e != hipSuccess) {
-        lpf_set_hip_error(e);
-        return LPF_ERR_LAUNCH;
-    }
+    if (lpf_reset_counter(scratch, s) != LPF_OK) return LPF_ERR_LAUNCH;   // long-pair counter
     const int64_t blocks = (P + TP_WAVES - 1) / TP_WAVES;
     hipLaunchKernelGGL(thresh_short_kernel, dim3((unsigned)(blocks < TP_GRID ? blocks : TP_GRID)), dim3(TP_BLOCK), 0, s,
                        A);

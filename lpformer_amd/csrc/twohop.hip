@@ -63,15 +63,10 @@ struct THArgs {
     int32_t *ws_stamp, *ws_cn;                  // [n_groups][n]
 };
 
-__device__ __forceinline__ bool th_sorted_has(const int32_t *a, int64_t lo, int64_t hi, int32_t key) {
-    const int64_t i = lpf_lower_bound(a, lo, hi, key);
-    return i < hi && a[i] == key;
-}
-
 // whether touched id c of source u (row [r0, r1)) is written
 __device__ __forceinline__ bool th_keep(const THArgs &A, int64_t u, int64_t r0, int64_t r1, int32_t c) {
     if ((A.flags & 2) && c == u) return false;
-    if ((A.flags & 1) && th_sorted_has(A.col, r0, r1, c)) return false;
+    if ((A.flags & 1) && lpf_sorted_has(A.col, r0, r1, c)) return false;
     return true;
 }
 
@@ -247,7 +242,7 @@ __global__ __launch_bounds__(TH_BLOCK) void twohop_group_kernel(THArgs A) {
                     if ((uint64_t)x < (uint64_t)A.n && stamp[x] == epoch) ++drop;
                 }
             if (tid == 0 && (A.flags & 2) && stamp[u] == epoch &&
-                !((A.flags & 1) && th_sorted_has(A.col, r0, r1, (int32_t)u)))
+                !((A.flags & 1) && lpf_sorted_has(A.col, r0, r1, (int32_t)u)))
                 ++drop;
             __syncthreads();                      // every thread has read m_sh
             if (drop) atomicSub(&m_sh, drop);
@@ -342,8 +337,8 @@ __global__ __launch_bounds__(POOL_BLOCK) void pool_extra_kernel(PoolArgs A) {
         bool keep = false;
         if (j < b1) {
             c = A.b_col[j];
-            keep = (uint64_t)c < (uint64_t)A.n && c != u && !th_sorted_has(A.exc_col, e0, e1, c) &&
-                   !th_sorted_has(A.a_col, a0, a1, c);
+            keep = (uint64_t)c < (uint64_t)A.n && c != u && !lpf_sorted_has(A.exc_col, e0, e1, c) &&
+                   !lpf_sorted_has(A.a_col, a0, a1, c);
         }
         const uint64_t bm = __ballot(keep);
         if (MODE && keep) {
@@ -490,7 +485,7 @@ __global__ __launch_bounds__(LPF_WAVE) void rank_interleave_kernel(ILArgs A) {
     for (int32_t d0 = 0; kept < kh && d0 < IL_MAX_DRAWS; d0 += LPF_WAVE) {
         const int32_t d = d0 + lane;
         const int32_t c = (int32_t)lpf_pad_draw(A.seed, u, (uint32_t)d, (uint32_t)A.n);
-        const bool ex = c != u && !th_sorted_has(A.exc_col, e0x, e1x, c);
+        const bool ex = c != u && !lpf_sorted_has(A.exc_col, e0x, e1x, c);
         const bool first = il_claim(keys, tmin, c, t_pad + d, ex);
         const uint64_t bm = __ballot(first);
         const int32_t pos = kept + __popcll(bm & ((1ull << lane) - 1ull));

@@ -30,9 +30,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib, graph, heuristics
+from . import _lib, graph, sources
 from ._lib import check, ptr
-from .evaluate import _as_2xp, _raw_stream
 
 # half-open [lo, hi) cells for evaluate.metrics_by_bin / explain.attention_profile:
 # unreachable, the same node, 1, 2, 3, 4-5 and 6 or more hops
@@ -49,16 +48,7 @@ ABI_MAX_GROUPS = 65535                # lpf_pair_bfs: 1 <= n_groups <= 65535
 WORKSPACE_MB = 2048
 
 
-def _check_edges(edges) -> torch.Tensor:
-    batch = _as_2xp(edges)
-    if batch.dtype.is_floating_point or batch.dtype.is_complex or batch.dtype == torch.bool:
-        raise ValueError("edges must hold integer node ids")
-    return batch
-
-
-def _check_options(max_dist, chunk, groups, workspace_mb):
-    if int(chunk) < 1:
-        raise ValueError("chunk must be positive")
+def _check_options(max_dist, groups, workspace_mb):
     if max_dist is not None:
         if isinstance(max_dist, bool) or not isinstance(max_dist, (int, np.integer)) or int(max_dist) < 1:
             raise ValueError(f"max_dist must be None or an integer >= 1; got {max_dist!r}")
@@ -73,18 +63,15 @@ def _check_options(max_dist, chunk, groups, workspace_mb):
 # ------------------------------------------------------------------------------------------------- host restatement
 def _neighbours(rowptr, col, nodes):
     """The concatenated rows ``nodes``."""
-    start = rowptr[nodes]
-    cnt = rowptr[nodes + 1] - start
-    flat = np.arange(int(cnt.sum()), dtype=np.int64) + np.repeat(start - (np.cumsum(cnt) - cnt), cnt)
-    return col[flat].astype(np.int64)
+    return col[sources.csr_rows(rowptr, nodes)[0]].astype(np.int64)
 
 
 def distance_reference(adj: graph.CSR, edges, *, max_dist=None, ignore_direct: bool = False) -> torch.Tensor:
     """``pair_distance`` of a host CSR in numpy (a CPU int32 tensor out): plain level-by-level frontier sets, one search
     per distinct first endpoint (one per pair where ``ignore_direct`` removes the pair's own edge).  The restatement the
     device kernel is tested against, and what ``pair_distance`` runs when there is no GPU."""
-    max_dist = _check_options(max_dist, 1, None, 1)
-    batch = _check_edges(edges).cpu().to(torch.int64).numpy()
+    max_dist = _check_options(max_dist, None, 1)
+    batch = sources.as_pairs(edges).cpu().to(torch.int64).numpy()
     a, b = batch[0], batch[1]
     n = int(adj.n)
     rowptr, col = np.asarray(adj.rowptr, np.int64), np.asarray(adj.col)
@@ -154,12 +141,12 @@ def pair_distance(source, edges, *, test_set: bool = False, max_dist=None, ignor
 
     The result is a device tensor and nothing is read back.  A host ``graph.CSR`` with CPU ``edges`` and no GPU present
     goes through ``distance_reference`` and gives a CPU tensor."""
-    max_dist = _check_options(max_dist, chunk, groups, workspace_mb)
-    chunk = min(int(chunk), (1 << 31) - 2)
-    batch = _check_edges(edges)
-    if isinstance(source, graph.CSR) and not batch.is_cuda and not torch.cuda.is_available():
-        return distance_reference(source, batch, max_dist=max_dist, ignore_direct=ignore_direct)
-    dev, adj, _, _ = heuristics._resolve(source, test_set, batch)
+    max_dist = _check_options(max_dist, groups, workspace_mb)
+    chunk = sources.clamp_chunk(chunk)
+    batch = sources.as_pairs(edges)
+    dev, adj, _, _ = sources.resolve(source, test_set, batch, who="pair_distance", host_ok=True)
+    if dev is None:
+        return distance_reference(adj, batch, max_dist=max_dist, ignore_direct=ignore_direct)
     batch = batch.to(dev, dtype=torch.int64).contiguous()
     P = batch.shape[1]
     with torch.cuda.device(dev):
@@ -172,9 +159,9 @@ def pair_distance(source, edges, *, test_set: bool = False, max_dist=None, ignor
         nbytes = int(hip.lpf_pair_bfs_workspace_bytes(adj.n, n_groups))
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
         scratch = torch.empty(m_max + 1, dtype=torch.int32, device=dev)
-        st = _raw_stream(dev)
-        for lo in range(0, P, chunk):
-            check(hip.lpf_pair_bfs(min(chunk, P - lo), adj.n, batch.data_ptr() + lo * 8, P, ptr(adj.rowptr),
+        st = sources.raw_stream(dev)
+        for lo, m in sources.chunks(P, chunk):
+            check(hip.lpf_pair_bfs(m, adj.n, batch.data_ptr() + lo * 8, P, ptr(adj.rowptr),
                                    ptr(adj.col), 0 if max_dist is None else max_dist, 1 if ignore_direct else 0,
                                    int(split_threshold), ptr(scratch), ptr(ws), n_groups,
                                    dist.data_ptr() + lo * 4, st), "lpf_pair_bfs")

@@ -19,12 +19,11 @@ from typing import Optional
 
 import torch
 
+from .sources import as_pairs, raw_stream
 
-def _as_2xp(edges: torch.Tensor) -> torch.Tensor:
-    edges = torch.as_tensor(edges)
-    if edges.dim() != 2 or 2 not in edges.shape:
-        raise ValueError("edges must be [P, 2] (the reference's split layout) or [2, P]")
-    return edges.t() if edges.shape[1] == 2 and edges.shape[0] != 2 else edges
+
+def _as_2xp(edges) -> torch.Tensor:
+    return as_pairs(edges, exc=None)        # score_edges takes ids of any dtype, as it always has
 
 
 # Full batches per stream from which recording the step pays.  Measured (tools/sweep_rate.py, 8 streams): recording the
@@ -176,10 +175,6 @@ def ranking_metrics(pos: torch.Tensor, neg: torch.Tensor) -> dict:
 INT32_MAX = 2 ** 31 - 1
 
 
-def _raw_stream(dev) -> int:
-    return torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
-
-
 def _scores(t, what: str) -> torch.Tensor:
     t = torch.as_tensor(t)
     if not t.is_floating_point():
@@ -218,7 +213,7 @@ def _shared_call(pos: torch.Tensor, neg: Optional[torch.Tensor], keys: torch.Ten
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         _lib.check(hip.lpf_rank_shared_f32(p, _lib.ptr(pos), m, _lib.ptr(neg) if m > 0 else None, _lib.ptr(keys),
                                            _lib.ptr(ws), nbytes, _lib.ptr(ge), _lib.ptr(gt), _lib.ptr(nan),
-                                           _raw_stream(dev)), "lpf_rank_shared_f32")
+                                           raw_stream(dev)), "lpf_rank_shared_f32")
     return ge, gt, nan
 
 
@@ -274,7 +269,7 @@ def _counts_rows(pos: torch.Tensor, neg: torch.Tensor):
     nan = torch.empty(2, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.hip().lpf_rank_rows_f32(p, k, _lib.ptr(pos), _lib.ptr(neg) if k > 0 else None, ld, _lib.ptr(ge),
-                                                _lib.ptr(gt), _lib.ptr(nan), _raw_stream(dev)), "lpf_rank_rows_f32")
+                                                _lib.ptr(gt), _lib.ptr(nan), raw_stream(dev)), "lpf_rank_rows_f32")
     return ge, gt, nan
 
 

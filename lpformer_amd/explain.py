@@ -21,7 +21,8 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from .evaluate import CN_BINS, _as_2xp, _raw_stream
+from .evaluate import CN_BINS
+from .sources import as_pairs, node_ids, raw_stream
 
 MAX_TOP = 32
 TYPE_NAMES = ("padding", "cn", "1-hop", ">1-hop")     # values of ``types``
@@ -128,7 +129,7 @@ def _reduce_device(tp, node, pa, pb, score, top: int, want_all: bool, max_entrie
     with torch.cuda.device(dev):
         _lib.check(_lib.hip().lpf_pair_explain_f32(
             bs, p(tp), p(node), p(pa), p(pb), p(score), max_entries, top, p(mass), p(ent), p(nodes), p(weights),
-            p(types), p(ppr_a), p(ppr_b), p(all_ptr), p(all_node), p(all_type), p(all_w), p(heavy), _raw_stream(dev)),
+            p(types), p(ppr_a), p(ppr_b), p(all_ptr), p(all_node), p(all_type), p(all_w), p(heavy), raw_stream(dev)),
             "lpf_pair_explain_f32")
     full = None
     if want_all:
@@ -160,8 +161,7 @@ def explain_from_scores(type_ptr, node, pa, pb, score, top: int, want_all: bool 
         raise ValueError("type_ptr must be [3, P + 1]")
     tp = tp.contiguous()
     node = torch.as_tensor(node).to(dev).reshape(-1)
-    if node.is_floating_point() or node.dtype == torch.bool:
-        raise TypeError(f"node must hold integer ids, got {node.dtype}")
+    node = node_ids(node, "node")
     pa, pb, score = (torch.as_tensor(t).to(dev, torch.float32).reshape(-1).contiguous() for t in (pa, pb, score))
     n_have = min(node.numel(), pa.numel(), pb.numel(), score.numel())
     if n_have >= 2 ** 31:
@@ -194,9 +194,7 @@ def explain(model, edges, top: int = 8, *, test_set: bool = False, adj_mask=None
         raise ValueError("weights must be 'top' or 'all'")
     if int(batch_size) < 1:
         raise ValueError("batch_size must be positive")
-    batch = _as_2xp(edges)
-    if batch.is_floating_point():
-        raise TypeError("edges must hold integer node ids")
+    batch = as_pairs(edges, exc=TypeError)
     n = int(model.num_nodes)
     if batch.numel() and (int(batch.min()) < 0 or int(batch.max()) >= n):
         raise IndexError(f"explain: edges hold node ids outside [0, {n})")

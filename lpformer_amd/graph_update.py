@@ -37,6 +37,7 @@ import torch
 from . import _lib, graph
 from .graph import CSR, DeviceCSR
 from .ppr import calc_ppr, calc_ppr_gpu
+from .sources import raw_stream
 
 # Flagged share of the sources above which the ordinary full producer runs instead (same result by definition: a speed
 # knob).  Measured on the MI355X (tools/graph_update_timing.py, profiles/graph_update_timing.json, table in DESIGN 5.11):
@@ -241,10 +242,6 @@ def _verify(old: CSR, unflagged: np.ndarray, k: int, rowptr, col, alpha, eps, nu
 
 
 # ------------------------------------------------------------------------------------------------ device path
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def affected_rows_device(ppr: DeviceCSR, mask: np.ndarray, bitmap_mode: int = -1):
     """``lpf_ppr_affected_rows``: (flag int32 [n], list int32 [n] -- ascending ids in its first ``count`` entries --,
     count int64 [1]) on the device of ``ppr``; ``mask``: bool [n] key nodes (host).  Nothing is read back."""
@@ -260,7 +257,7 @@ def affected_rows_device(ppr: DeviceCSR, mask: np.ndarray, bitmap_mode: int = -1
     ws = torch.empty(max(int(lib.lpf_ppr_affected_workspace_bytes(n)), 256), dtype=torch.uint8, device=dev)
     _lib.check(lib.lpf_ppr_affected_rows(n, _lib.ptr(ppr.rowptr), _lib.ptr(ppr.col), _lib.ptr(bitmap), int(bitmap_mode),
                                          _lib.ptr(flag), _lib.ptr(lst), _lib.ptr(count), _lib.ptr(ws), ws.numel(),
-                                         _stream(dev)), "lpf_ppr_affected_rows")
+                                         raw_stream(dev)), "lpf_ppr_affected_rows")
     return flag[:n], lst, count
 
 
@@ -290,7 +287,7 @@ def push_sources_device(rowptr: torch.Tensor, col: torch.Tensor, n: int, sources
         _lib.check(lib.lpf_ppr_push_f64_sources(n, _lib.ptr(rowptr), _lib.ptr(col), S, _lib.ptr(sources), float(alpha),
                                                 float(eps), n_waves, _lib.ptr(ws), ws_bytes, _lib.ptr(pool_col),
                                                 _lib.ptr(pool_val), cap, _lib.ptr(row_off), _lib.ptr(row_len),
-                                                _lib.ptr(counters), _stream(dev)), "lpf_ppr_push_f64_sources")
+                                                _lib.ptr(counters), raw_stream(dev)), "lpf_ppr_push_f64_sources")
         _, nnz, bad, _ = (int(x) for x in counters.tolist())
         if bad:
             raise _lib.LpfError(f"lpf_ppr_push_f64_sources: {bad} rows exceeded the 1/(alpha*eps) list bound")
@@ -315,7 +312,7 @@ def splice_device(old: DeviceCSR, sources: torch.Tensor, row_off, row_len, pool_
     _lib.check(lib.lpf_ppr_splice_csr(n, _lib.ptr(old.rowptr), _lib.ptr(old.col), _lib.ptr(old.val), S,
                                       _lib.ptr(sources), _lib.ptr(row_off), _lib.ptr(row_len), _lib.ptr(pool_col),
                                       _lib.ptr(pool_val), nnz_pool, _lib.ptr(out_rowptr), _lib.ptr(out_col),
-                                      _lib.ptr(out_val), out_nnz, _lib.ptr(ws), ws_bytes, _stream(dev)),
+                                      _lib.ptr(out_val), out_nnz, _lib.ptr(ws), ws_bytes, raw_stream(dev)),
                "lpf_ppr_splice_csr")
     return out_rowptr, out_col[:out_nnz], out_val[:out_nnz]
 

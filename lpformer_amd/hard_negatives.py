@@ -27,8 +27,8 @@ import torch
 
 from . import _lib, graph, heuristics
 from ._lib import check, ptr
-from .evaluate import _as_2xp
 from .recommend import plan_chunks, segment_topk
+from .sources import as_pairs, node_ids, raw_stream, resolve
 
 HEURISTICS = ("cn", "aa", "ra", "ppr", "feat")
 TWOHOP_KINDS = ("cn", "aa", "ra")
@@ -47,58 +47,13 @@ class HardNegatives(NamedTuple):
     spare: torch.Tensor        # int64 [U]: entry k/2 + 1 of each list, taken when a positive's other endpoint is listed
 
 
-def _stream(dev):
-    return torch._C._cuda_getCurrentRawStream(dev.index)
-
-
-def _as_device_csr(g, dev, what, need_val=False):
-    if isinstance(g, graph.CSR):
-        g = heuristics._cached(heuristics._UPLOADS, g, lambda: g.to_device(dev)) if dev is not None else g
-    if not isinstance(g, graph.DeviceCSR):
-        raise TypeError(f"{what} must be a graph.CSR or a graph.DeviceCSR")
-    if not g.rowptr.is_cuda:
-        raise _lib.LpfError(f"{what} must live on an MI355X; lpformer_amd has no CPU fallback")
-    if need_val and g.val is None:
-        raise ValueError(f"{what} needs values")
-    return g
-
-
-def _resolve(source, test_set: bool, like: torch.Tensor):
-    """(device, adjacency DeviceCSR, PPR DeviceCSR or None, node features or None) of ``source``: a LinkTransformer, a
-    CSR / DeviceCSR adjacency, or the explicit pieces (adjacency, PPR or None, x or None)."""
-    if isinstance(source, (tuple, list)):
-        if len(source) != 3:
-            raise TypeError("explicit pieces are (adjacency, PPR or None, x or None)")
-        adj, ppr, x = source
-        if isinstance(adj, graph.DeviceCSR):
-            dev = adj.rowptr.device
-        else:
-            if not torch.cuda.is_available():
-                raise _lib.LpfError("hard negatives need an MI355X; lpformer_amd has no CPU fallback")
-            dev = like.device if like.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        adj = _as_device_csr(adj, dev, "the adjacency")
-        if ppr is not None:
-            ppr = _as_device_csr(ppr, dev, "the PPR matrix", need_val=True)
-            if ppr.n != adj.n or ppr.rowptr.device != adj.rowptr.device:
-                raise ValueError("the PPR matrix and the adjacency must have the same nodes and device")
-        return adj.rowptr.device, adj, ppr, x
-    return heuristics._resolve(source, test_set, like)
-
-
 def _workspace(n: int, dev):
     groups = int(max(1, min(MAX_GROUPS, WORKSPACE_BUDGET // (24 * max(n, 1)))))
     nbytes = int(_lib.hip().lpf_twohop_workspace_bytes(n, groups))
     return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev), groups
 
 
-def _node_ids(nodes, what):
-    t = torch.as_tensor(nodes)
-    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
-        raise TypeError(f"{what} must hold integer node ids")
-    return t
-
-
-class _TwoHop:
+class TwoHop:
     """The count pass of ``nodes`` (device int64 [S]) and ``fill(lo, hi)`` for ranges of whole sources."""
 
     def __init__(self, adj: graph.DeviceCSR, nodes: torch.Tensor, kinds, flags: int, split_threshold: int):
@@ -111,7 +66,7 @@ class _TwoHop:
         if S:
             check(_lib.hip().lpf_twohop_count(S, adj.n, ptr(nodes), ptr(adj.rowptr), ptr(adj.col), self.thr, self.flags,
                                               ptr(self.scratch), ptr(self.ws), self.groups, ptr(self.counts),
-                                              _stream(dev)), "lpf_twohop_count")
+                                              raw_stream(dev)), "lpf_twohop_count")
 
     def fill(self, lo: int, hi: int, total: int):
         """(seg_ptr int64 [hi - lo + 1], col int32 [total], cn int32, aa, ra float32 -- None where not asked for)."""
@@ -127,7 +82,7 @@ class _TwoHop:
             check(_lib.hip().lpf_twohop_fill(hi - lo, adj.n, self.nodes.data_ptr() + lo * 8, ptr(adj.rowptr),
                                              ptr(adj.col), ptr(w_aa), ptr(w_ra), self.thr, self.flags,
                                              ptr(self.scratch), ptr(self.ws), self.groups, ptr(seg), total, ptr(col),
-                                             ptr(cn), ptr(aa), ptr(ra), _stream(dev)), "lpf_twohop_fill")
+                                             ptr(cn), ptr(aa), ptr(ra), raw_stream(dev)), "lpf_twohop_fill")
         return seg, col, cn, aa, ra
 
 
@@ -149,13 +104,13 @@ def twohop_rows(source, nodes, kinds=("cn", "ra"), *, test_set: bool = False, ex
     kinds = tuple(kinds)
     if [k for k in kinds if k not in TWOHOP_KINDS] or len(set(kinds)) != len(kinds):
         raise ValueError(f"kinds must be distinct members of {TWOHOP_KINDS}; got {kinds!r}")
-    src = _node_ids(nodes, "nodes")
+    src = node_ids(nodes, "nodes")
     if src.dim() != 1:
         raise ValueError("nodes must be a 1-D tensor [S]")
-    dev, adj, _, _ = _resolve(source, test_set, src)
+    dev, adj, _, _ = resolve(source, test_set, src, who="twohop_rows", pieces=True)
     with torch.cuda.device(dev):
         src = src.to(dev, torch.int64).contiguous()
-        th = _TwoHop(adj, src, kinds, 3 if exclude else 0, split_threshold)
+        th = TwoHop(adj, src, kinds, 3 if exclude else 0, split_threshold)
         total = int(th.counts.sum()) if src.numel() else 0
         seg, col, cn, aa, ra = th.fill(0, src.numel(), total)
     vals = {"cn": cn, "aa": aa, "ra": ra}
@@ -175,7 +130,7 @@ def _check_args(pos_edges, k, heur, seed, max_pairs):
         raise TypeError("seed must be an integer")
     if int(max_pairs) < 1:
         raise ValueError("max_pairs must be positive")
-    edges = _as_2xp(_node_ids(pos_edges, "pos_edges"))
+    edges = as_pairs(pos_edges, what="pos_edges", exc=TypeError)
     return edges, heur, int(seed) & 0xFFFFFFFFFFFFFFFF
 
 
@@ -196,7 +151,7 @@ def node_lists(adj: graph.DeviceCSR, ppr: Optional[graph.DeviceCSR], xd: Optiona
 
     want = tuple(h for h in TWOHOP_KINDS if h in heur)
     with phase("two-hop rows"):
-        th = _TwoHop(adj, nodes, want, 3, split_threshold)
+        th = TwoHop(adj, nodes, want, 3, split_threshold)
     b = ppr if ppr is not None else graph.DeviceCSR(torch.zeros(n + 1, dtype=torch.int64, device=dev),
                                                     torch.zeros(0, dtype=torch.int32, device=dev),
                                                     torch.zeros(0, dtype=torch.float32, device=dev), n)
@@ -213,7 +168,7 @@ def node_lists(adj: graph.DeviceCSR, ppr: Optional[graph.DeviceCSR], xd: Optiona
         with phase("pool"):
             x_cnt = torch.zeros(m, dtype=torch.int64, device=dev)
             check(hip.lpf_pool_extra_count(m, n, ptr(nodes_c), ptr(a_ptr), ptr(a_col), ptr(b.rowptr), ptr(b.col),
-                                           ptr(adj.rowptr), ptr(adj.col), ptr(x_cnt), _stream(dev)),
+                                           ptr(adj.rowptr), ptr(adj.col), ptr(x_cnt), raw_stream(dev)),
                   "lpf_pool_extra_count")
             x_ptr = torch.zeros(m + 1, dtype=torch.int64, device=dev)
             torch.cumsum(x_cnt, 0, out=x_ptr[1:])
@@ -227,7 +182,7 @@ def node_lists(adj: graph.DeviceCSR, ppr: Optional[graph.DeviceCSR], xd: Optiona
                 check(hip.lpf_pool_fill(m, n, ptr(nodes_c), ptr(a_ptr), ptr(a_col), ptr(a_cn), ptr(a_aa), ptr(a_ra),
                                         ptr(b.rowptr), ptr(b.col), ptr(b.val), ptr(adj.rowptr), ptr(adj.col),
                                         ptr(x_ptr), ptr(x_col), ptr(x_val), X, T, ptr(pairs), ptr(vals.get("cn")),
-                                        ptr(vals.get("aa")), ptr(vals.get("ra")), ptr(vals.get("ppr")), _stream(dev)),
+                                        ptr(vals.get("aa")), ptr(vals.get("ra")), ptr(vals.get("ppr")), raw_stream(dev)),
                       "lpf_pool_fill")
             pool_ptr = a_ptr + x_ptr
         if "feat" in heur:
@@ -242,7 +197,7 @@ def node_lists(adj: graph.DeviceCSR, ppr: Optional[graph.DeviceCSR], xd: Optiona
         with phase("interleave"):
             check(hip.lpf_rank_interleave(m, n, ptr(nodes_c), H, kh, ptr(ids), ptr(top), ptr(cnt), ptr(adj.rowptr),
                                           ptr(adj.col), seed, lists.data_ptr() + lo * kh * 8,
-                                          ranked.data_ptr() + lo * 4, _stream(dev)), "lpf_rank_interleave")
+                                          ranked.data_ptr() + lo * 4, raw_stream(dev)), "lpf_rank_interleave")
     return lists, ranked
 
 
@@ -294,7 +249,7 @@ def heart_negatives(source, pos_edges, k: int = 500, *, test_set: bool = False, 
         need(source[1], source[2])              # (before anything touches the device)
     elif isinstance(source, (graph.CSR, graph.DeviceCSR)):
         need(None, None)
-    dev, adj, ppr, x = _resolve(source, test_set, edges)
+    dev, adj, ppr, x = resolve(source, test_set, edges, who="heart_negatives", pieces=True)
     need(ppr, x)
     n = adj.n
     if edges.numel() and (int(edges.min()) < 0 or int(edges.max()) >= n):
@@ -309,7 +264,7 @@ def heart_negatives(source, pos_edges, k: int = 500, *, test_set: bool = False, 
                 u = int(nodes[int(room.argmin())])
                 raise ValueError(f"node {u} has only {int(room.min())} non-neighbours; k / 2 = {kh} negatives need "
                                  "that many")
-        xd = _h._device_features(x, dev) if "feat" in heur else None
+        xd = _h.device_features(x, dev) if "feat" in heur else None
         # one spare entry per node: a positive (a, b) that is not an edge of the adjacency may find b in list(a)
         full, ranked1 = node_lists(adj, ppr, xd, nodes, kh + 1, heur, seed, max_pairs, split_threshold, timings)
         inv = inv.reshape(2, P)

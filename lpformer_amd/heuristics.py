@@ -12,31 +12,16 @@ selection uses, and the per-node weight tables (1 / ln deg, 1 / deg) are cached 
 """
 from __future__ import annotations
 
-import weakref
-
 import torch
 
-from . import _lib, graph
+from . import _lib, graph, sources
 from ._lib import check, ptr
-from .evaluate import _as_2xp
 
 KINDS = ("cn", "aa", "ra", "ppr", "feat")
 
-# id(graph object) -> (weak reference to it, cached value): per-graph state kept while the graph lives, checked by
-# identity like the model's (kind, id(obj)) -> (obj, ...) caches
+# per-object state (sources.per_object): the weight tables of a graph, the device copy of a host feature tensor
 _TABLES: dict = {}
-_UPLOADS: dict = {}
-
-
-def _cached(cache: dict, obj, make):
-    hit = cache.get(id(obj))
-    if hit is not None and hit[0]() is obj:
-        return hit[1]
-    val = make()
-    key = id(obj)
-    cache[key] = (weakref.ref(obj), val)
-    weakref.finalize(obj, cache.pop, key, None)
-    return val
+_FEATURES: dict = {}
 
 
 def weight_tables(g: graph.DeviceCSR):
@@ -47,49 +32,18 @@ def weight_tables(g: graph.DeviceCSR):
         w_aa = torch.where(deg > 1, 1.0 / torch.log(deg.clamp_min(2.0)), torch.zeros_like(deg))
         w_ra = torch.where(deg > 0, 1.0 / deg.clamp_min(1.0), torch.zeros_like(deg))
         return w_aa.to(torch.float32).contiguous(), w_ra.to(torch.float32).contiguous()
-    return _cached(_TABLES, g, make)
+    return sources.per_object(_TABLES, g, make)
 
 
-def _device_features(x: torch.Tensor, dev) -> torch.Tensor:
+def device_features(x: torch.Tensor, dev) -> torch.Tensor:
     """fp32 node features on ``dev``: ``x`` itself when it lives there, else a device copy cached per tensor object
     and version (a host-resident data["x"] is not uploaded again on every call)."""
     if x.device == dev and x.dtype == torch.float32:
         return x.detach()
-    hit = _cached(_UPLOADS, x, lambda: [None, None])      # (keyed by the data dict's own tensor object)
+    hit = sources.per_object(_FEATURES, x, lambda: [None, None])      # (keyed by the data dict's own tensor object)
     if hit[0] != x._version or hit[1] is None or hit[1].device != dev:
         hit[0], hit[1] = x._version, x.detach().to(dev, dtype=torch.float32)
     return hit[1]
-
-
-def _stream(device):
-    return torch._C._cuda_getCurrentRawStream(device.index)
-
-
-def _resolve(source, test_set: bool, edges: torch.Tensor):
-    """(device, adjacency DeviceCSR, PPR DeviceCSR or None, node features or None) of ``source``."""
-    from .link_transformer import LinkTransformer
-    if isinstance(source, LinkTransformer):
-        dev = source.device
-        if dev.type != "cuda":
-            raise _lib.LpfError("pair_heuristics: the model must live on an MI355X; lpformer_amd has no CPU fallback")
-        with torch.cuda.device(dev):
-            adj = source._device_graph("mask", source._data_obj("mask", test_set))
-            ppr = source._device_graph("ppr", source._data_obj("ppr", test_set))
-        return dev, adj, ppr, source.data["x"]
-    if isinstance(source, graph.DeviceCSR):
-        if not source.rowptr.is_cuda:
-            raise _lib.LpfError("pair_heuristics: the DeviceCSR must live on an MI355X")
-        return source.rowptr.device, source, None, None
-    if isinstance(source, graph.CSR):
-        if not torch.cuda.is_available():
-            raise _lib.LpfError("pair_heuristics needs an MI355X; lpformer_amd has no CPU fallback")
-        dev = edges.device if edges.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        adj = _cached(_UPLOADS, source,
-                      lambda: graph.CSR(source.rowptr, source.col, None, source.n).to_device(dev))
-        if adj.rowptr.device != dev:
-            adj = graph.CSR(source.rowptr, source.col, None, source.n).to_device(dev)
-        return dev, adj, None, None
-    raise TypeError("source must be a LinkTransformer, a graph.CSR or a graph.DeviceCSR")
 
 
 def _check_kinds(kinds):
@@ -118,20 +72,16 @@ def pair_heuristics(source, edges, *, test_set: bool = False, kinds=("cn", "aa",
     ``chunk``: pairs per launch.  ``split_threshold``: walked-row length above which a pair gets a whole workgroup
     (negative: the library default ``LPF_HEUR_SPLIT_DEFAULT``).  Nothing is read back to the host."""
     kinds = _check_kinds(kinds)
-    if int(chunk) < 1:
-        raise ValueError("chunk must be positive")
-    chunk = min(int(chunk), (1 << 31) - 2)
-    batch = _as_2xp(edges)
-    if batch.dtype.is_floating_point or batch.dtype == torch.bool:
-        raise ValueError("edges must hold integer node ids")
-    dev, adj, ppr, x = _resolve(source, test_set, batch)
+    chunk = sources.clamp_chunk(chunk)
+    batch = sources.as_pairs(edges)
+    dev, adj, ppr, x = sources.resolve(source, test_set, batch, who="pair_heuristics")
     if ("ppr" in kinds and ppr is None) or ("feat" in kinds and x is None):
         raise ValueError("'ppr' and 'feat' need a LinkTransformer source (its PPR matrix and node features)")
     batch = batch.to(dev, dtype=torch.int64).contiguous()
     P = batch.shape[1]
     out = {}
     with torch.cuda.device(dev):
-        st = _stream(dev)
+        st = sources.raw_stream(dev)
         want = [k for k in ("cn", "aa", "ra") if k in kinds]
         if want:
             cn = torch.empty(P, dtype=torch.int32, device=dev) if "cn" in want else None
@@ -140,9 +90,7 @@ def pair_heuristics(source, edges, *, test_set: bool = False, kinds=("cn", "aa",
             w_aa, w_ra = weight_tables(adj) if ("aa" in want or "ra" in want) else (None, None)
             if P:
                 scratch = torch.empty(min(P, chunk) + 1, dtype=torch.int32, device=dev)
-                for lo in range(0, P, chunk):
-                    m = min(chunk, P - lo)
-
+                for lo, m in sources.chunks(P, chunk):
                     def at(t):
                         return None if t is None else t.data_ptr() + lo * t.element_size()
                     check(_lib.hip().lpf_pair_heuristics_f32(
@@ -157,7 +105,7 @@ def pair_heuristics(source, edges, *, test_set: bool = False, kinds=("cn", "aa",
                                                         ptr(ppr.val), ptr(v), st), "lpf_csr_lookup_f32")
                 out[name] = v
         if "feat" in kinds:
-            out["feat"] = feature_cosine(_device_features(x, dev), batch, chunk)
+            out["feat"] = feature_cosine(device_features(x, dev), batch, chunk)
     return out
 
 

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib, graph
 from ._lib import check, ptr
+from .sources import model_graphs, node_ids, raw_stream
 
 MAX_K = 1024                 # LPF_TOPK_MAX_K (include/lpformer_hip.h)
 CANDIDATE_MODES = ("ppr", "all", "2hop")
@@ -60,9 +61,7 @@ def _check_args(sources, k, candidates):
     """Argument checks that need no device.  Returns (sources as a 1-D int64 tensor, explicit candidates or None)."""
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_K:
         raise ValueError(f"k must be an integer in [1, {MAX_K}]; got {k!r}")
-    src = torch.as_tensor(sources)
-    if src.dtype.is_floating_point or src.dtype.is_complex or src.dtype == torch.bool:
-        raise TypeError("sources must hold integer node ids")
+    src = node_ids(sources, "sources")
     if src.dim() != 1:
         raise ValueError("sources must be a 1-D tensor [S]")
     explicit = None
@@ -70,22 +69,19 @@ def _check_args(sources, k, candidates):
         if candidates not in CANDIDATE_MODES:
             raise ValueError(f"candidates must be one of {CANDIDATE_MODES} or an int tensor [S, M]; got {candidates!r}")
     else:
-        explicit = torch.as_tensor(candidates)
-        if explicit.dtype.is_floating_point or explicit.dtype.is_complex or explicit.dtype == torch.bool:
-            raise TypeError("explicit candidates must hold integer node ids")
+        explicit = node_ids(candidates, "explicit candidates")
         if explicit.dim() != 2 or explicit.shape[0] != src.shape[0]:
             raise ValueError("explicit candidates must be [S, M] with one row per source")
     return src, explicit
 
 
-def _exclusion(model, exclude, test_set, dev):
+def _exclusion(model, exclude, adj, dev):
     if exclude is None:
         return None
     if isinstance(exclude, str):
         if exclude != "adj":
             raise ValueError("exclude must be 'adj', None, a graph.CSR or a graph.DeviceCSR")
-        with torch.cuda.device(dev):
-            return model._device_graph("mask", model._data_obj("mask", test_set))
+        return adj
     if isinstance(exclude, graph.DeviceCSR):
         if exclude.rowptr.device != dev:
             raise ValueError("the exclusion DeviceCSR must live on the model's device")
@@ -105,10 +101,6 @@ def _range_check(src: torch.Tensor, n: int, what: str):
         raise IndexError(f"{what}: node id {int(bad)} outside [0, {n})")
 
 
-def _stream(dev):
-    return torch._C._cuda_getCurrentRawStream(dev.index)
-
-
 def generate_candidates(n: int, sources: torch.Tensor, include, min_ppr: float, exclude, exclude_self: bool,
                         split_threshold: int = -1):
     """The candidate counts of device int64 ``sources`` ([S] int64) and a function ``fill(lo, hi, total)`` that returns the
@@ -121,7 +113,7 @@ def generate_candidates(n: int, sources: torch.Tensor, include, min_ppr: float, 
     exc = (ptr(exclude.rowptr), ptr(exclude.col)) if exclude is not None else (None, None)
     counts = torch.zeros(S, dtype=torch.int64, device=dev)
     scratch = torch.empty(S + 1, dtype=torch.int32, device=dev)
-    st = _stream(dev)
+    st = raw_stream(dev)
     if S:
         check(hip.lpf_rec_candidate_count(S, n, ptr(sources), *inc, float(min_ppr), *exc, int(bool(exclude_self)),
                                           int(split_threshold), ptr(scratch), ptr(counts), st),
@@ -134,7 +126,7 @@ def generate_candidates(n: int, sources: torch.Tensor, include, min_ppr: float, 
             offset = torch.cumsum(seg, 0) - seg
             check(hip.lpf_rec_candidate_fill(hi - lo, n, sources.data_ptr() + lo * 8, *inc, float(min_ppr), *exc,
                                              int(bool(exclude_self)), int(split_threshold), ptr(scratch), ptr(offset),
-                                             total, ptr(pairs), _stream(dev)), "lpf_rec_candidate_fill")
+                                             total, ptr(pairs), raw_stream(dev)), "lpf_rec_candidate_fill")
         return pairs
     return counts, fill
 
@@ -142,8 +134,8 @@ def generate_candidates(n: int, sources: torch.Tensor, include, min_ppr: float, 
 def twohop_candidates(adj, sources: torch.Tensor, exclude_adj: bool, exclude_self: bool, split_threshold: int = -1):
     """``generate_candidates`` for ``candidates="2hop"``: every v with a common neighbour with u on ``adj`` (one row of
     A A, ``lpf_twohop_count`` / ``lpf_twohop_fill``), minus N(u) with ``exclude_adj``, minus u with ``exclude_self``."""
-    from .hard_negatives import _TwoHop
-    th = _TwoHop(adj, sources, (), (1 if exclude_adj else 0) | (2 if exclude_self else 0), split_threshold)
+    from .hard_negatives import TwoHop
+    th = TwoHop(adj, sources, (), (1 if exclude_adj else 0) | (2 if exclude_self else 0), split_threshold)
 
     def fill(lo: int, hi: int, total: int) -> torch.Tensor:
         seg, col, _, _, _ = th.fill(lo, hi, total)
@@ -170,7 +162,7 @@ def segment_topk(seg_ptr: torch.Tensor, score: torch.Tensor, cand: torch.Tensor,
         scratch = torch.empty(S + 1, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
             check(_lib.hip().lpf_segment_topk_f32(S, ptr(seg_ptr), ptr(score), ptr(cand), int(k), ptr(scratch),
-                                                  ptr(ids), ptr(out), ptr(counts), _stream(dev)),
+                                                  ptr(ids), ptr(out), ptr(counts), raw_stream(dev)),
                   "lpf_segment_topk_f32")
     return ids, out, counts
 
@@ -201,9 +193,7 @@ def recommend(model, score_func, sources, k: int = 100, *, candidates="ppr", min
         raise ValueError("max_pairs and batch_size must be positive")
     if model.training:
         raise NotImplementedError("recommend needs model.eval(), as score_pairs does")
-    dev = model.device
-    if dev.type != "cuda":
-        raise _lib.LpfError("recommend: the model must live on an MI355X; lpformer_amd has no CPU fallback")
+    dev, adj, ppr = model_graphs(model, test_set, "recommend")
     n = int(model.num_nodes)
     _range_check(src, n, "recommend: sources")
     S = src.numel()
@@ -219,18 +209,14 @@ def recommend(model, score_func, sources, k: int = 100, *, candidates="ppr", min
             def fill(lo, hi, total):
                 return torch.stack([src[lo:hi].repeat_interleave(M), cand[lo:hi].reshape(-1)])
         else:
-            include = None
-            if candidates == "ppr":
-                include = model._device_graph("ppr", model._data_obj("ppr", test_set))
             if candidates == "2hop":
                 if exclude not in ("adj", None):
                     raise ValueError("candidates='2hop' takes exclude='adj' or None: the two-hop row kernel drops the "
                                      "row of the adjacency it walks")
-                n_cand, fill = twohop_candidates(model._device_graph("mask", model._data_obj("mask", test_set)), src,
-                                                 exclude == "adj", exclude_self, split_threshold)
+                n_cand, fill = twohop_candidates(adj, src, exclude == "adj", exclude_self, split_threshold)
             else:
-                exc = _exclusion(model, exclude, test_set, dev)
-                n_cand, fill = generate_candidates(n, src, include, min_ppr, exc, exclude_self, split_threshold)
+                n_cand, fill = generate_candidates(n, src, ppr if candidates == "ppr" else None, min_ppr,
+                                                   _exclusion(model, exclude, adj, dev), exclude_self, split_threshold)
             counts_host = n_cand.cpu().numpy()       # the one read-back: it sizes the chunks and their outputs
         if h is None:
             h = model.propagate(test_set=test_set)

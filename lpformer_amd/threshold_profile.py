@@ -32,9 +32,8 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _lib, graph
+from . import _lib, graph, sources
 from ._lib import check, ptr
-from .evaluate import _as_2xp, _raw_stream
 
 MAX_T = 32                                  # LPF_THRESH_MAX_T (include/lpformer_hip.h)
 DEFAULT_GRID = (0, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1)
@@ -143,13 +142,6 @@ def check_thresholds(thresholds) -> np.ndarray:
     return th
 
 
-def _check_edges(edges) -> torch.Tensor:
-    batch = _as_2xp(edges)
-    if batch.dtype.is_floating_point or batch.dtype == torch.bool:
-        raise ValueError("edges must hold integer node ids")
-    return batch
-
-
 # ------------------------------------------------------------------------------------------------- host restatement
 def _rt1(x: np.ndarray) -> np.ndarray:
     one = np.float32(1)
@@ -164,10 +156,7 @@ def _rt2(x: np.ndarray) -> np.ndarray:
 def _row_keys(rowptr, col, nodes, n):
     """Keys position * n + column of the rows ``nodes`` (one row per position; ascending and unique), and the flat
     indexes of those entries."""
-    start = rowptr[nodes]
-    cnt = rowptr[nodes + 1] - start
-    pos = np.repeat(np.arange(nodes.size, dtype=np.int64), cnt)
-    flat = np.arange(int(cnt.sum()), dtype=np.int64) + np.repeat(start - (np.cumsum(cnt) - cnt), cnt)
+    flat, pos = sources.csr_rows(rowptr, nodes)
     return pos * np.int64(n) + col[flat].astype(np.int64), flat
 
 
@@ -215,7 +204,7 @@ def profile_reference(adj: graph.CSR, ppr: graph.CSR, edges, thresholds=DEFAULT_
     """``threshold_profile`` of host CSR containers in numpy (CPU tensors out): the restatement the device kernel is
     tested against, and what ``threshold_profile`` runs when there is no GPU."""
     th = check_thresholds(thresholds)
-    batch = _check_edges(edges).cpu().to(torch.int64).numpy()
+    batch = sources.as_pairs(edges).cpu().to(torch.int64).numpy()
     if ppr.val is None:
         raise ValueError("the PPR matrix needs values")
     if int(adj.n) != int(ppr.n):
@@ -240,50 +229,6 @@ def profile_reference(adj: graph.CSR, ppr: graph.CSR, edges, thresholds=DEFAULT_
 
 
 # ------------------------------------------------------------------------------------------------------ device path
-def _on_device(g, dev) -> graph.DeviceCSR:
-    from .heuristics import _UPLOADS, _cached
-    if isinstance(g, graph.DeviceCSR):
-        if g.rowptr.device != dev:
-            raise _lib.LpfError("threshold_profile: both graphs must live on the same MI355X")
-        return g
-    up = _cached(_UPLOADS, g, lambda: g.to_device(dev))     # a host CSR is uploaded (and cached) once
-    return up if up.rowptr.device == dev else g.to_device(dev)
-
-
-def _resolve(source, test_set: bool, mode_cn, batch: torch.Tensor):
-    """(device or None for the host path, adjacency, PPR matrix, mode_cn) of ``source``."""
-    from .link_transformer import LinkTransformer
-    if isinstance(source, LinkTransformer):
-        dev = source.device
-        if dev.type != "cuda":
-            raise _lib.LpfError("threshold_profile: the model must live on an MI355X (profile host CSR containers "
-                                "with source=(adj, ppr) instead)")
-        with torch.cuda.device(dev):
-            adj = source._device_graph("mask", source._data_obj("mask", test_set))
-            ppr = source._device_graph("ppr", source._data_obj("ppr", test_set))
-        return dev, adj, ppr, (source.mask == "cn") if mode_cn is None else bool(mode_cn)
-    if not (isinstance(source, (tuple, list)) and len(source) == 2 and
-            all(isinstance(g, (graph.CSR, graph.DeviceCSR)) for g in source)):
-        raise TypeError("source must be a LinkTransformer or a pair (adj, ppr) of graph.CSR / graph.DeviceCSR")
-    adj, ppr = source
-    if ppr.val is None:
-        raise ValueError("the PPR matrix needs values")
-    if int(adj.n) != int(ppr.n):
-        raise ValueError("the adjacency and the PPR matrix must describe the same nodes")
-    on_gpu = [g.rowptr.device for g in source if isinstance(g, graph.DeviceCSR) and g.rowptr.is_cuda]
-    if any(isinstance(g, graph.DeviceCSR) and not g.rowptr.is_cuda for g in source):
-        raise _lib.LpfError("threshold_profile: a DeviceCSR must live on an MI355X (pass host graphs as graph.CSR)")
-    if on_gpu:
-        dev = on_gpu[0]
-    elif batch.is_cuda:
-        dev = batch.device
-    elif torch.cuda.is_available():
-        dev = torch.device("cuda", torch.cuda.current_device())
-    else:
-        return None, adj, ppr, bool(mode_cn)
-    return dev, _on_device(adj, dev), _on_device(ppr, dev), bool(mode_cn)
-
-
 @torch.no_grad()
 def threshold_profile(source, edges, thresholds=DEFAULT_GRID, *, test_set: bool = False, per_pair: bool = False,
                       chunk: int = 1 << 20, split_threshold: int = -1, mode_cn: Optional[bool] = None) -> ThresholdProfile:
@@ -300,11 +245,12 @@ def threshold_profile(source, edges, thresholds=DEFAULT_GRID, *, test_set: bool 
     Results are device tensors and nothing is read back to the host during the sweep; host ``graph.CSR`` containers
     with CPU edges and no GPU present go through ``profile_reference`` and give CPU tensors."""
     th = check_thresholds(thresholds)
-    if int(chunk) < 1:
-        raise ValueError("chunk must be positive")
-    chunk = min(int(chunk), (1 << 31) - 2)
-    batch = _check_edges(edges)
-    dev, adj, ppr, cn_mode = _resolve(source, test_set, mode_cn, batch)
+    chunk = sources.clamp_chunk(chunk)
+    batch = sources.as_pairs(edges)
+    dev, adj, ppr, _ = sources.resolve(source, test_set, batch, who="threshold_profile", pieces=True, host_ok=True)
+    if ppr is None:
+        raise TypeError("source must be a LinkTransformer or a pair (adj, ppr) of graph.CSR / graph.DeviceCSR")
+    cn_mode = getattr(source, "mask", None) == "cn" if mode_cn is None else bool(mode_cn)
     if dev is None:
         return profile_reference(adj, ppr, batch, th, mode_cn=cn_mode, per_pair=per_pair)
     batch = batch.to(dev, dtype=torch.int64).contiguous()
@@ -316,10 +262,9 @@ def threshold_profile(source, edges, thresholds=DEFAULT_GRID, *, test_set: bool 
         ne = torch.zeros(3, T, dtype=torch.int64, device=dev)
         pp = torch.empty(P, 3, T, dtype=torch.int32, device=dev) if per_pair else None
         if P:
-            st = _raw_stream(dev)
+            st = sources.raw_stream(dev)
             scratch = torch.empty(min(P, chunk) + 1, dtype=torch.int32, device=dev)
-            for lo in range(0, P, chunk):
-                m = min(chunk, P - lo)
+            for lo, m in sources.chunks(P, chunk):
                 check(_lib.hip().lpf_threshold_profile(
                     m, adj.n, batch.data_ptr() + lo * 8, P, ptr(adj.rowptr), ptr(adj.col), ptr(ppr.rowptr),
                     ptr(ppr.col), ptr(ppr.val), T, C.cast(th_host, C.c_void_p), 1 if cn_mode else 0,

@@ -8,7 +8,7 @@ import torch
 import lpformer_amd
 from lpformer_amd import data as D
 from lpformer_amd import evaluate as E
-from lpformer_amd import graph
+from lpformer_amd import graph, sources
 from lpformer_amd.heuristics import pair_heuristics
 from tests.golden_util import Fixture
 
@@ -214,6 +214,25 @@ def test_ppr_and_feature_kinds(case):
     model.data["x"] = torch.nn.Parameter(torch.from_numpy(fx["x"]).to(DEV))
     hp = pair_heuristics(model, torch.from_numpy(pairs), kinds="feat")
     assert float((hp["feat"].cpu() - want).abs().max()) <= 1e-6
+
+
+def test_model_sources_are_the_resident_graphs():
+    """The analysis entry points read the resident graphs the selection reads, and make no copy of their own."""
+    fx = Fixture("lp_all_d64_residual_valtest")
+    model, _ = _build(fx)
+    e = torch.from_numpy(fx["batch"].astype(np.int64))
+    lpformer_amd.pair_heuristics(model, e, test_set=True)
+    resident = len(model._graphs)
+    lpformer_amd.pair_distance(model, e, test_set=True)
+    lpformer_amd.threshold_profile(model, e, test_set=True)
+    lpformer_amd.pair_heuristics(model, e, test_set=True, kinds=("ppr",))
+    assert len(model._graphs) == resident
+    for ts in (False, True):
+        dev, adj, ppr = sources.model_graphs(model, ts, "test")
+        assert dev == model.device
+        assert adj is model._device_graph("mask", model._data_obj("mask", ts))
+        assert ppr is model._device_graph("ppr", model._data_obj("ppr", ts))
+    assert adj is not sources.model_graphs(model, False, "test")[1]       # (this fixture's splits differ)
 
 
 def _np_hits(pos, neg, k):

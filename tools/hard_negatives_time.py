@@ -9,7 +9,7 @@ import numpy as np, torch
 import lpformer_amd
 from lpformer_amd import data as D
 from lpformer_amd import evaluate as E
-from lpformer_amd.hard_negatives import _TwoHop
+from lpformer_amd.hard_negatives import TwoHop
 
 P = int(os.environ.get("LPF_P", "32768"))
 K = int(os.environ.get("LPF_K", "500"))
@@ -65,7 +65,7 @@ for name in os.environ.get("LPF_CFGS", "collab ppa").split():
     adj = model._device_graph("mask", model._data_obj("mask", False))
     for thr in SPLITS:
         def passes():
-            th = _TwoHop(adj, hn.nodes, ("ra",), 3, thr)
+            th = TwoHop(adj, hn.nodes, ("ra",), 3, thr)
             lo = 0
             step = max(1, hn.nodes.numel() // 8)
             cnt = th.counts.cpu().numpy()

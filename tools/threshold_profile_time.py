@@ -9,7 +9,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import lpformer_amd
-from lpformer_amd import data as D
+from lpformer_amd import data as D, sources
 from lpformer_amd.threshold_profile import DEFAULT_GRID, threshold_profile
 
 REPS = int(os.environ.get("LPF_REPS", "20"))
@@ -79,8 +79,7 @@ for th in grid:
 source = next(m for m in models if m is not None)
 prof = threshold_profile(source, batch, DEFAULT_GRID, per_pair=True)
 print(prof.table(), flush=True)
-adj = source._device_graph("mask", source._data_obj("mask", False))
-ppr = source._device_graph("ppr", source._data_obj("ppr", False))
+_, adj, ppr = sources.model_graphs(source, False, "threshold_profile_time")
 deg = (adj.rowptr[1:] - adj.rowptr[:-1])
 plen = (ppr.rowptr[1:] - ppr.rowptr[:-1])
 walked = torch.stack([deg[batch[0]], deg[batch[1]], torch.minimum(plen[batch[0]], plen[batch[1]])]).cpu().numpy()
