@@ -987,6 +987,38 @@ int lpf_pair_bfs(int64_t P, int64_t n, const int64_t *pairs, int64_t pairs_ld, c
                  void *workspace, int64_t n_groups, int32_t *dist, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Pair walk counts (pair_walks.hip): W_l(a, b) = (A^l)[a, b] for l = 1 .. max_len <= 4 on the typing adjacency -- what
+ * the Katz index sum_l beta^l W_l sums (the "Katz" baseline of HeaRT / OGB comparisons, truncated at 3 there).  The
+ * reference has no such code.  Both symbols were added within ABI 16: the addition changes no existing symbol, so
+ * LPF_ABI_VERSION stays.
+ * ---------------------------------------------------------------------------------------------- */
+/* Bytes of workspace for n_groups resident workgroups: a 16-byte header (the unit ticket), then per group one 64-bit
+ * word per node (a 32-bit epoch stamp over a 32-bit payload): 16 + n_groups * 8 n. */
+int64_t lpf_pair_walks_workspace_bytes(int64_t n, int64_t n_groups);
+/* The CSR has sorted, unique columns and a SYMMETRIC pattern (values ignored; a non-symmetric pattern is outside the
+ * contract).  W_l counts the walks of l stored entries: stored self-loops count as the entries they are, a == b is no
+ * special case (W_2(a, a) = deg(a)), an id outside [0, n) gives 0 for every l.
+ * The caller hands the m pairs over ORIENTED and GROUPED: pair j = (s, t) = (pairs[j], pairs[pair_stride + j]), s the
+ * endpoint that is spread and t the one walked from (the counts are the same either way), and unit_ptr int32[m + 1]
+ * cuts the list into units: unit u holds the pairs [unit_ptr[u], unit_ptr[u + 1]), all with the SAME s; the entries
+ * after the last unit's end hold m.  Persistent 256-thread workgroups take units by an atomic ticket, spread s once
+ * per unit into dense epoch-stamped state over all n nodes (the indicator of N(s) and, for max_len = 4, the two-hop
+ * counts |N(s) & N(c)|, by integer atomic max and add) and walk each pair of the unit two hops from t, summing what
+ * they meet in 64-bit unsigned integers.  The caller bounds the counts: W_l <= maxdeg^(l - 1) must stay below 2^63.
+ * ignore_direct != 0: for a pair that is a unit of its own, every transition x -> y with {x, y} = {s, t} is skipped at
+ * every step -- counting on a copy of the graph without the stored entries (s, t) and (t, s); the caller makes every
+ * pair that is a stored entry a one-pair unit (a pair that is no entry is unaffected wherever it stands).
+ * walks_out int64[m][max_len]: row j = W_1 .. W_max_len of pair j; pairs no unit covers are left untouched.  The result
+ * is a pure function of (graph, pair, options): not of the position, the orientation, the units, n_groups or timing;
+ * two runs are bitwise equal.  Integers only.
+ * workspace: lpf_pair_walks_workspace_bytes(n, n_groups) bytes, 16-byte aligned; header and state are zeroed here,
+ * once per call.  1 <= max_len <= 4 and 1 <= n_groups <= 65535 (checked first: LPF_ERR_INVALID whatever m is);
+ * m < 2^31 - 1, n < 2^31 - 3.  m == 0 returns LPF_OK without a launch. */
+int lpf_pair_walks(int64_t m, int64_t n, const int64_t *pairs, int64_t pair_stride, const int64_t *rowptr,
+                   const int32_t *col, int32_t max_len, int32_t ignore_direct, const int32_t *unit_ptr,
+                   void *workspace, int64_t n_groups, int64_t *walks_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training step of the pair stage (pair_train.hip): the forward of get_pos_encodings
  * (link_transformer.py:182-211) and LinkAttention.message + PyG softmax + scatter-sum (layers.py:193-224) with the
  * state a backward pass needs, and the gradients torch autograd derives from them (the reference's training step,

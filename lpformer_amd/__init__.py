@@ -10,6 +10,8 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
     pair_heuristics                     CN / Adamic-Adar / Resource Allocation (+ PPR, feature cosine) of pairs
     pair_distance, DIST_BINS            shortest-path hops per pair (device bidirectional BFS) and its bins for
                                         metrics_by_bin / attention_profile
+    pair_walks, pair_katz               walk counts (A^l)[a, b], l <= 4, per pair (device meet-in-the-middle kernel) and
+                                        the truncated Katz index; katz_from_walks, walks_reference (numpy restatement)
     recommend                           top-K new links per source node (device candidates, scoring, top-K)
     explain, explain_from_scores        per-pair attention attribution: top nodes, mass per type, entropy (device
                                         segmented reduction); pairs_of (a recommend result's pairs), attention_profile
@@ -29,6 +31,7 @@ from .graph import RemovedEdges  # noqa: F401
 from .graph_update import ppr_affected_sources, update_data, update_graph, update_ppr  # noqa: F401
 from .hard_negatives import HardNegatives, heart_negatives, twohop_rows  # noqa: F401
 from .heuristics import pair_heuristics  # noqa: F401
+from .katz import katz_from_walks, pair_katz, pair_walks, walks_reference  # noqa: F401
 from .graphed import GraphedScorer, PlannedScorer  # noqa: F401
 from .link_transformer import MLP, LinkTransformer, mlp_score  # noqa: F401
 from .ppr import calc_ppr, calc_ppr_gpu, get_ppr, load_or_calc_ppr, ppr_coo  # noqa: F401
@@ -41,4 +44,5 @@ __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_
            "pair_heuristics", "recommend", "Recommendations", "heart_negatives", "twohop_rows",
            "HardNegatives", "ppr_affected_sources", "update_ppr", "update_data", "update_graph", "explain", "explain_from_scores",
            "pairs_of", "attention_profile", "Explanation", "threshold_profile", "suggest_thresholds", "ThresholdProfile",
-           "TrainEdges", "train_epoch", "fit", "pair_distance", "DIST_BINS"]
+           "TrainEdges", "train_epoch", "fit", "pair_distance", "DIST_BINS", "pair_walks",
+           "pair_katz", "katz_from_walks", "walks_reference"]

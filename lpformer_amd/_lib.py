@@ -104,6 +104,8 @@ HIP_PROTOTYPES = {
     "lpf_twohop_fill": [i64, i64, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp],
     "lpf_pair_bfs_workspace_bytes": [i64, i64],
     "lpf_pair_bfs": [i64, i64, vp, i64, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp],
+    "lpf_pair_walks_workspace_bytes": [i64, i64],
+    "lpf_pair_walks": [i64, i64, vp, i64, vp, vp, i32, i32, vp, vp, i64, vp, vp],
     "lpf_pool_extra_count": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "lpf_pool_fill": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp,
                       vp],
@@ -148,7 +150,7 @@ _RESTYPE = {"lpf_strerror": C.c_char_p, "lpf_last_hip_error": C.c_char_p, "lpf_h
             "lpf_ppr_affected_workspace_bytes": C.c_int64, "lpf_ppr_splice_workspace_bytes": C.c_int64,
             "lpf_gemm_tn_workspace_floats": C.c_int64, "lpf_layernorm_bwd_workspace_floats": C.c_int64,
             "lpf_train_partial_blocks": C.c_int64, "lpf_pair_rows_piece_floats": C.c_int64,
-            "lpf_rank_shared_workspace_bytes": C.c_int64}
+            "lpf_rank_shared_workspace_bytes": C.c_int64, "lpf_pair_walks_workspace_bytes": C.c_int64}
 
 
 class LpfError(RuntimeError):
