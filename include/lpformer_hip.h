@@ -1019,6 +1019,51 @@ int lpf_pair_walks(int64_t m, int64_t n, const int64_t *pairs, int64_t pair_stri
                    void *workspace, int64_t n_groups, int64_t *walks_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Uniform negatives that avoid known edges (neg_sample.hip): K targets per source, or node pairs, drawn on the device
+ * against a "known" CSR with sorted, unique int32 columns in [0, n) (values ignored; the pattern need not be
+ * symmetric).  The reference draws torch.randint pairs (src/train/train_model.py:64) and has no edge-aware sampler.
+ * Both symbols were added within ABI 16: the addition changes no existing symbol, so LPF_ABI_VERSION stays.
+ *
+ * The draw, all in uint64 (wrapping):
+ *   mix64(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   G = 0x9E3779B97F4A7C15;  key(seed, i) = mix64(seed + G (i + 1));  u(seed, i, j) = mix64(key(seed, i) + G (j + 1))
+ *   node(u, n) = (u * n) >> 64                      (the high half of the 128-bit product)
+ * -- splitmix64 started at the slot's key.  Every output is a pure function of (seed, slot, graph, options): not of the
+ * launch shape, of timing or of the other slots of the call; two runs are bitwise equal.  Integers only.
+ * ---------------------------------------------------------------------------------------------- */
+/* Largest K of lpf_negative_rows (the per-row hash set holds 2,048 ids) and largest max_draws of either call. */
+#define LPF_NEGATIVE_MAX_K 1024
+#define LPF_NEGATIVE_MAX_DRAWS (1 << 30)
+#define LPF_NEGATIVE_ROW_DRAWS_DEFAULT (1 << 20)
+#define LPF_NEGATIVE_PAIR_DRAWS_DEFAULT (1 << 16)
+/* Row r has the source s = sources[r] and the stream c_j = node(u(seed, row_base + r, j), n), j = 0, 1, ...  A draw is
+ * accepted iff c_j != s, c_j is not in row s of the CSR and c_j is no earlier accepted draw of this row.  out int64
+ * [R][K], row r = the first min(K, avail) accepted draws in stream order, avail = n - deg(s) - [s not in row s]; the
+ * remaining entries are -1.  A row stops after max_draws draws (1 .. LPF_NEGATIVE_MAX_DRAWS) with -1 in what is left;
+ * a source outside [0, n) gives a row of -1.  short_rows (one int64, zeroed by the call, R == 0 included) counts the
+ * rows with any -1.  Consequences: the K'-prefix of a row is the row for K'; a row does not depend on the other rows of
+ * the call, only on its slot row_base + r -- a call over rows [lo, hi) with row_base + lo gives those rows --; a source
+ * named in several rows gets a different row each time.
+ * One wavefront per row, lane l of round t takes draw 64 t + l; membership is a binary search, repeats go through an LDS
+ * hash set (ids claimed by compare-and-swap, the smallest draw index kept by integer atomic min: the earliest draw wins
+ * within a round and against earlier ones), accepted lanes are ranked by ballot.  1 <= K <= LPF_NEGATIVE_MAX_K,
+ * R < 2^31 - 1, n < 2^31 - 1 (LPF_ERR_INVALID otherwise, before anything runs). */
+int lpf_negative_rows(int64_t R, int64_t n, const int64_t *sources, int32_t K, const int64_t *rowptr,
+                      const int32_t *col, uint64_t seed, int64_t row_base, int32_t max_draws, int64_t *out,
+                      int64_t *short_rows, void *stream);
+/* Slot i draws, for j = next[i], next[i] + 1, ..., the pair a = node(u(seed, slot_base + i, 2 j), n),
+ * b = node(u(seed, slot_base + i, 2 j + 1), n), accepted iff a != b and neither (a, b) nor (b, a) is a stored entry.
+ * The first accepted pair goes to pairs[i], pairs[pair_stride + i] (int64) and the draw index after it to next[i]
+ * (int32, input AND output: a caller makes a slot continue its stream by calling again; start it at 0; negative reads
+ * as 0).  Only slots with active[i] != 0 are touched (uint8[M]; NULL: all of them).  A slot that reaches j = max_draws
+ * (1 .. LPF_NEGATIVE_MAX_DRAWS) without a pair holds (-1, -1), next[i] = max_draws, and is counted in unresolved (one
+ * int64, zeroed by the call, M == 0 included): a graph without a free pair ends with every slot at (-1, -1).  One lane
+ * per slot.  M < 2^31 - 1, n < 2^31 - 1, pair_stride >= M. */
+int lpf_negative_pairs(int64_t M, int64_t n, const int64_t *rowptr, const int32_t *col, uint64_t seed,
+                       int64_t slot_base, int32_t max_draws, const uint8_t *active, int32_t *next, int64_t *pairs,
+                       int64_t pair_stride, int64_t *unresolved, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training step of the pair stage (pair_train.hip): the forward of get_pos_encodings
  * (link_transformer.py:182-211) and LinkAttention.message + PyG softmax + scatter-sum (layers.py:193-224) with the
  * state a backward pass needs, and the gradients torch autograd derives from them (the reference's training step,

@@ -21,9 +21,15 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
     update_ppr, update_data, update_graph   graph edits with an exact incremental PPR refresh (ppr_affected_sources)
     TrainEdges, train_epoch, fit        the training epoch: the reference's per-batch edge mask made exactly on the
                                         device (repeated pairs included), the loop, and epochs with early stopping
+    negative_rows, negative_pairs       uniform negatives that avoid known edges, drawn on the device: K targets per
+                                        source / M distinct pairs; UniformNegatives (fresh non-edges per training step
+                                        for train_epoch(negatives=...)), negatives_reference (numpy restatement)
+    link_split                          edge list + features -> a data dict with train / valid / test positives and
+                                        edge-aware negatives, ready for fit and evaluate_model
     graph, data                         CSR containers and the data-dict builder
 """
 from . import evaluate, graph, mask_delta, readers  # noqa: F401
+from .data import link_split  # noqa: F401
 from .distance import DIST_BINS, pair_distance  # noqa: F401
 from .epoch import TrainEdges, fit, train_epoch  # noqa: F401
 from .explain import Explanation, attention_profile, explain, explain_from_scores, pairs_of  # noqa: F401
@@ -32,6 +38,7 @@ from .graph_update import ppr_affected_sources, update_data, update_graph, updat
 from .hard_negatives import HardNegatives, heart_negatives, twohop_rows  # noqa: F401
 from .heuristics import pair_heuristics  # noqa: F401
 from .katz import katz_from_walks, pair_katz, pair_walks, walks_reference  # noqa: F401
+from .negatives import UniformNegatives, negative_pairs, negative_rows, negatives_reference  # noqa: F401
 from .graphed import GraphedScorer, PlannedScorer  # noqa: F401
 from .link_transformer import MLP, LinkTransformer, mlp_score  # noqa: F401
 from .ppr import calc_ppr, calc_ppr_gpu, get_ppr, load_or_calc_ppr, ppr_coo  # noqa: F401
@@ -45,4 +52,5 @@ __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_
            "HardNegatives", "ppr_affected_sources", "update_ppr", "update_data", "update_graph", "explain", "explain_from_scores",
            "pairs_of", "attention_profile", "Explanation", "threshold_profile", "suggest_thresholds", "ThresholdProfile",
            "TrainEdges", "train_epoch", "fit", "pair_distance", "DIST_BINS", "pair_walks",
-           "pair_katz", "katz_from_walks", "walks_reference"]
+           "pair_katz", "katz_from_walks", "walks_reference", "negative_rows", "negative_pairs", "UniformNegatives",
+           "negatives_reference", "link_split"]

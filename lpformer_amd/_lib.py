@@ -106,6 +106,8 @@ HIP_PROTOTYPES = {
     "lpf_pair_bfs": [i64, i64, vp, i64, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp],
     "lpf_pair_walks_workspace_bytes": [i64, i64],
     "lpf_pair_walks": [i64, i64, vp, i64, vp, vp, i32, i32, vp, vp, i64, vp, vp],
+    "lpf_negative_rows": [i64, i64, vp, i32, vp, vp, u64, i64, i32, vp, vp, vp],
+    "lpf_negative_pairs": [i64, i64, vp, vp, u64, i64, i32, vp, vp, vp, i64, vp, vp],
     "lpf_pool_extra_count": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "lpf_pool_fill": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp,
                       vp],

@@ -58,6 +58,74 @@ def build_data(edge_index, x, num_nodes: int, *, edge_weight=None, eps: float = 
     return data
 
 
+def link_split(edge_index, x, num_nodes: int, *, val_frac: float = 0.05, test_frac: float = 0.10,
+               negatives: str = "shared", num_neg: Optional[int] = None, seed: int = 0, use_val_in_test: bool = False,
+               **build_data_kw) -> dict:
+    """A trainable, evaluable data dict from a user's own graph: ``build_data``'s graph entries plus the split tensors
+    ``train_pos, train_pos_val, valid_pos, valid_neg, test_pos, test_neg`` of ``readers.py`` (int64 CPU tensors), ready
+    for ``fit`` and ``evaluate.evaluate_model``.
+
+    1. the undirected edges of ``edge_index`` ([2, E] or [E, 2], either or both directions) are canonicalised: self-loops
+       dropped, one row (min, max) per pair, ascending;
+    2. they are permuted by ``torch.randperm`` under ``seed`` and cut into valid (``int(val_frac * E)`` rows), test
+       (``int(test_frac * E)``) and train (the rest), in that order;
+    3. ``build_data`` runs on the training edges in both directions (``build_data_kw``: eps, alpha, ppr_device, ...);
+       with ``use_val_in_test`` the valid edges join the test-time graph (``val_edge_index``);
+    4. ``train_pos_val``: a ``randperm`` subset of ``train_pos`` of ``valid_pos``' size, as the readers make it;
+    5. ``valid_neg`` / ``test_neg`` come from ``lpformer_amd.negatives`` under ``seed`` and avoid ALL edges (train,
+       valid and test).  ``negatives="shared"``: [M, 2] each, M = ``num_neg`` or the split's number of positives, one
+       call over both splits' slots (valid first), so no unordered pair occurs twice within or across the two.
+       ``negatives="rows"``: [P, num_neg, 2] (default 500, HeaRT's), the sources the first column of the split's
+       positives, the test rows on the slots after the valid ones: the two sets are drawn from different streams (a
+       source both splits hold may still meet a target twice).  A graph too dense to supply them raises ``ValueError``.
+
+    The same arguments give the same dict, with or without a GPU (the sampler is a pure function of its seed)."""
+    from . import negatives as N
+    if negatives not in ("shared", "rows"):
+        raise ValueError(f"negatives must be 'shared' or 'rows'; got {negatives!r}")
+    for key in ("edge_weight", "val_edge_index"):       # (the split decides the order and the roles of the edges)
+        if key in build_data_kw:
+            raise TypeError(f"link_split builds {key} itself; it takes an unweighted edge list")
+    if not (0.0 <= float(val_frac) and 0.0 <= float(test_frac) and float(val_frac) + float(test_frac) < 1.0):
+        raise ValueError("val_frac and test_frac must be >= 0 and sum to less than 1")
+    n = int(num_nodes)
+    ei = np.asarray(torch.as_tensor(edge_index).cpu().numpy() if isinstance(edge_index, torch.Tensor) else edge_index,
+                    dtype=np.int64)
+    if ei.ndim != 2 or 2 not in ei.shape:
+        raise ValueError("edge_index must be [2, E] or [E, 2]")
+    if ei.shape[0] != 2:
+        ei = ei.T
+    if ei.size and (ei.min() < 0 or ei.max() >= n):
+        raise IndexError(f"edge_index holds node ids outside [0, {n})")
+    lo, hi = np.minimum(ei[0], ei[1]), np.maximum(ei[0], ei[1])
+    key = np.unique((lo * np.int64(n) + hi)[lo != hi])
+    canon = torch.from_numpy(np.stack([key // n, key % n], axis=1))             # [E, 2], ascending
+    E = canon.shape[0]
+    g = torch.Generator().manual_seed(int(seed))
+    canon = canon[torch.randperm(E, generator=g)]
+    n_val, n_test = int(float(val_frac) * E), int(float(test_frac) * E)
+    valid_pos, test_pos, train_pos = canon[:n_val], canon[n_val:n_val + n_test], canon[n_val + n_test:]
+    tr = train_pos.t().numpy()
+    both = np.concatenate([tr, tr[::-1]], axis=1)
+    both = both[:, np.argsort(both[0] * np.int64(n) + both[1], kind="stable")]
+    val_ei = valid_pos.t().numpy() if (use_val_in_test and n_val) else None
+    data = build_data(both, x, n, val_edge_index=val_ei, **build_data_kw)
+    data["edge_index"] = torch.from_numpy(np.ascontiguousarray(both))
+    data["train_pos"], data["valid_pos"], data["test_pos"] = train_pos, valid_pos, test_pos
+    data["train_pos_val"] = train_pos[torch.randperm(train_pos.shape[0], generator=g)[:n_val]]
+    known = graph.mask_csr(np.stack([key // n, key % n]), n, symmetric=True)    # every edge of every split
+    if negatives == "shared":
+        m_val, m_test = (n_val, n_test) if num_neg is None else (int(num_neg), int(num_neg))
+        neg = N.negative_pairs(known, m_val + m_test, seed=int(seed)).cpu().t().contiguous()
+        data["valid_neg"], data["test_neg"] = neg[:m_val], neg[m_val:]
+    else:
+        k = 500 if num_neg is None else int(num_neg)
+        data["valid_neg"] = N.negative_rows(known, valid_pos[:, 0], k, seed=int(seed), as_pairs=True).cpu()
+        data["test_neg"] = N.negative_rows(known, test_pos[:, 0], k, seed=int(seed), as_pairs=True,
+                                           row_base=n_val).cpu()
+    return data
+
+
 def chung_lu_graph(n: int, n_edges: int, gamma: float = 2.5, seed: int = 0, max_weight: int = 0):
     """Power-law (Chung-Lu) simple undirected graph: expected degree of node i ~ (i + i0)^(-1/(gamma-1)).
     Returns (edge_index [2, 2E] both directions sorted, edge_weight or None)."""
