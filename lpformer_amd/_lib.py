@@ -1,4 +1,5 @@
-"""ctypes binding of the two C-ABI shared objects (include/lpformer_hip.h).
+"""ctypes binding of the two C-ABI shared objects, derived at import from include/lpformer_hip.h: the header is the only
+place an entry point or an ABI constant is written.
 
 There is no fallback: if ``liblpformer_hip.so`` is missing or a call fails, the caller gets an exception.
 """
@@ -6,158 +7,124 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "liblpformer_hip.so")
 HOST_LIB_PATH = os.path.join(_HERE, "liblpformer_host.so")
 
-ABI_VERSION = 16
-FLAG_RELU = 1
-SELECT_ERR_NODE_RANGE, SELECT_ERR_ITEM_CAP, SELECT_ERR_ENTRY_CAP = 1, 2, 4
-ROWS_PERM_LB_WORDS = 1025      # LPF_ROWS_PERM_LB_WORDS (include/lpformer_hip.h)
-SELECT4_BLOCK = 64             # LPF_SELECT4_BLOCK
-
-i32, i64, f32, f64, u32, u64, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_uint32, C.c_uint64, C.c_void_p
-
-# name -> argument types (every entry point returns int unless listed in _RESTYPE)
-HIP_PROTOTYPES = {
-    "lpf_abi_version": [],
-    "lpf_strerror": [C.c_int],
-    "lpf_last_hip_error": [],
-    "lpf_device_info": [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int],
-    "lpf_gcn_norm_csr": [i64, vp, vp, vp, vp, vp, vp],
-    "lpf_spmm_csr_f32": [i64, i32, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, u32, vp, i64, vp],
-    "lpf_gemm_f32": [i64, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp, i64, u32, vp],
-    "lpf_layernorm_bwd_f32": [i64, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp],
-    "lpf_layernorm_bwd_workspace_floats": [i32],
-    "lpf_layernorm_relu_bwd_f32": [i64, i32, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp],
-    "lpf_layernorm_relu_drop_bwd_f32": [i64, i32, vp, i64, vp, i64, vp, vp, f32, u64, vp, i64, vp, vp, vp, vp, vp],
-    "lpf_gemm_tn_f32": [i64, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp],
-    "lpf_gemm_tn_colsum_f32": [i64, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp],
-    "lpf_gemm_tn_workspace_floats": [i64, i32, i32],
-    "lpf_gemm_f32_out_bf16": [i64, i32, i32, vp, i64, vp, i64, vp, vp, i64, vp, i64, u32, vp],
-    "lpf_gcn_layer_fused_f32": [i32, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, u32, vp,
-                                vp, vp, i64, vp],
-    "lpf_spmm_row_parts_f32": [i32, vp, i64, vp, vp, vp, i64, vp, vp],
-    "lpf_spmm_row_parts_bf16p": [i32, vp, i64, vp, vp, vp, i64, vp, vp],
-    "lpf_gcn_layer_fused_train_f32": [i32, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, u32, vp, vp,
-                                      vp, i64, vp, i64, f32, u64, vp],
-    "lpf_gcn_layer_fused_bf16": [i32, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, u32, vp,
-                                 vp, vp, i64, vp],
-    "lpf_spmm_csr_bf16": [i64, i32, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp, u32, vp, i64, vp],
-    "lpf_layernorm_f32": [i64, i32, vp, i64, vp, vp, vp, i64, u32, vp],
-    "lpf_pair_gather_f32": [i64, i32, vp, i64, i64, vp, i64, vp, i64, vp, i64, vp],
-    "lpf_select_plan_blocks": [i64],
-    "lpf_select_plan": [i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp],
-    "lpf_select_run": [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, i32, vp, vp, i64,
-                       i32, vp],
-    "lpf_select3_plan": [i64, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i64, vp, vp, vp],
-    "lpf_select3_run": [i64, vp, vp, vp, i64, vp, vp, vp, vp, f32, f32, f32, i32, vp, vp, i64, i32, vp],
-    "lpf_select4": [i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, i64, i32, vp],
-    "lpf_select4_regions": [i64, vp, vp, vp, i64, vp, vp, i64, vp, vp],
-    "lpf_select_export": [i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, vp, vp, vp],
-    "lpf_pair_scores_f32": [i32, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp],
-    "lpf_pair_softmax_gather_f32": [i32, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp],
-    "lpf_pair_explain_f32": [i64, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "lpf_pair_attention_fused_f32": [i32, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp],
-    "lpf_pair_attention_fused_bf16": [i32, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp],
-    "lpf_pair_attention_flip_f32": [i32, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp],
-    "lpf_pair_attention_flip_zbf16": [i32, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp],
-    "lpf_pair_attention_merge_f32": [i64, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp],
-    "lpf_pair_attention_rows_f32": [i32, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp,
-                                    i64, vp, i64, vp],
-    "lpf_pair_attention_rows_zbf16": [i32, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp,
-                                      i64, vp, i64, vp],
-    "lpf_pair_attention_rows_perm_f32": [i32, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp,
-                                         vp, i64, vp, i64, vp, vp, vp, vp],
-    "lpf_pair_attention_rows_perm_zbf16": [i32, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32,
-                                           vp, vp, i64, vp, i64, vp, vp, vp, vp],
-    "lpf_pair_attention_rows4_f32": [i32, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp,
-                                     vp, vp, vp, vp, i32, vp, vp, i64, vp, i64, vp, vp, vp],
-    "lpf_pair_attention_rows4_zbf16": [i32, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp,
-                                       vp, vp, vp, vp, i32, vp, vp, i64, vp, i64, vp, vp, vp],
-    "lpf_tail_chain_rows_perm_f32": [i64, i32, i32, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                     vp, vp, vp],
-    "lpf_tail_chain_rows_perm_bf16": [i64, i32, i32, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                      vp, vp, vp],
-    "lpf_pair_rows_piece_floats": [i32],
-    "lpf_tail_chain_rows_f32": [i64, i32, i32, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp],
-    "lpf_tail_chain_rows_bf16": [i64, i32, i32, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp],
-    "lpf_tail_chain_merge_f32": [i64, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp,
-                                 vp, vp, vp],
-    "lpf_tail_chain_merge_bf16": [i64, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp,
-                                 vp, vp, vp],
-    "lpf_rowdot_sigmoid_f32": [i64, i32, vp, i64, vp, f32, vp, vp, vp],
-    "lpf_tail_chain_f32": [i64, i32, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp,
-                           vp, vp],
-    "lpf_ppr_filter_count": [i64, vp, vp, i32, f32, vp, vp],
-    "lpf_ppr_filter_fill": [i64, vp, vp, vp, i32, f32, vp, vp, vp, vp],
-    "lpf_self_ppr": [i64, vp, vp, vp, vp, vp, vp, vp],
-    "lpf_csr_lookup_f32": [i64, i64, vp, vp, vp, vp, vp, vp, vp],
-    "lpf_pair_heuristics_f32": [i64, i64, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
-    "lpf_rec_candidate_count": [i64, i64, vp, vp, vp, vp, f32, vp, vp, i32, i32, vp, vp, vp],
-    "lpf_rec_candidate_fill": [i64, i64, vp, vp, vp, vp, f32, vp, vp, i32, i32, vp, vp, i64, vp, vp],
-    "lpf_segment_topk_f32": [i64, vp, vp, vp, i32, vp, vp, vp, vp, vp],
-    "lpf_twohop_workspace_bytes": [i64, i64],
-    "lpf_twohop_count": [i64, i64, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp],
-    "lpf_twohop_fill": [i64, i64, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp],
-    "lpf_pair_bfs_workspace_bytes": [i64, i64],
-    "lpf_pair_bfs": [i64, i64, vp, i64, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp],
-    "lpf_pair_walks_workspace_bytes": [i64, i64],
-    "lpf_pair_walks": [i64, i64, vp, i64, vp, vp, i32, i32, vp, vp, i64, vp, vp],
-    "lpf_negative_rows": [i64, i64, vp, i32, vp, vp, u64, i64, i32, vp, vp, vp],
-    "lpf_negative_pairs": [i64, i64, vp, vp, u64, i64, i32, vp, vp, vp, i64, vp, vp],
-    "lpf_pool_extra_count": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "lpf_pool_fill": [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp,
-                      vp],
-    "lpf_rank_interleave": [i64, i64, vp, i32, i32, vp, vp, vp, vp, vp, u64, vp, vp, vp],
-    "lpf_threshold_profile": [i64, i64, vp, i64, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp],
-    "lpf_batch_cover": [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp],
-    "lpf_rank_rows_f32": [i64, i64, vp, vp, i64, vp, vp, vp, vp],
-    "lpf_rank_shared_workspace_bytes": [i64, i64],
-    "lpf_rank_shared_f32": [i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp],
-    "lpf_ppr_push_workspace_bytes": [i64, i64, C.c_double, C.c_double],
-    "lpf_ppr_push_f64": [i64, vp, vp, C.c_double, C.c_double, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp],
-    "lpf_ppr_push_f64_sources": [i64, vp, vp, i64, vp, C.c_double, C.c_double, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp],
-    "lpf_ppr_affected_workspace_bytes": [i64],
-    "lpf_ppr_affected_rows": [i64, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp],
-    "lpf_ppr_splice_workspace_bytes": [i64, i64, i64],
-    "lpf_ppr_splice_csr": [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, i64, vp],
-    "lpf_ppr_pack_workspace_bytes": [i64, i64],
-    "lpf_ppr_pack_csr": [i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp],
-    "lpf_train_partial_blocks": [i64],
-    "lpf_pe_hidden_fwd_f32": [i64, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp],
-    "lpf_pe_hidden_bwd_f32": [i64, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp],
-    "lpf_colsum_f32": [i64, i32, vp, i64, vp, vp, vp],
-    "lpf_pair_attention_train_fwd_f32": [i64, i64, i32, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp,
-                                         vp],
-    "lpf_segment_rows_sum_f32": [i64, i32, vp, vp, vp, i64, vp, i64, vp],
-    "lpf_pair_attention_train_bwd_f32": [i64, i64, i32, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp,
-                                         vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp],
-    "lpf_pair_scatter_add_f32": [i64, i32, vp, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp],
-    "lpf_dense_chain_f32": [i64, i32, vp, i64, vp, i64, i64, i32, vp, i32, vp, vp, i64, vp, vp, u32, vp, i32, vp, vp, i64,
-                            vp, vp],
-    "lpf_dense_chain_side_f32": [i64, i32, vp, i64, vp, i64, i64, i32, vp, i32, vp, vp, i64, vp, vp, u32, vp, i32, vp, vp, i64,
-                            vp, vp, i64, i32, vp, i64, vp],
-}
-HOST_PROTOTYPES = {
-    "lpf_ppr_push_cpu": [i64, vp, vp, f64, f64, vp, C.POINTER(vp), C.POINTER(vp), i32],
-    "lpf_ppr_push_cpu_sources": [i64, vp, vp, f64, f64, i64, vp, vp, C.POINTER(vp), C.POINTER(vp), i32],
-    "lpf_host_free": [vp],
-    "lpf_host_abi_version": [],
-}
-_RESTYPE = {"lpf_strerror": C.c_char_p, "lpf_last_hip_error": C.c_char_p, "lpf_host_free": None,
-            "lpf_ppr_push_workspace_bytes": C.c_int64, "lpf_twohop_workspace_bytes": C.c_int64, "lpf_pair_bfs_workspace_bytes": C.c_int64, "lpf_select_plan_blocks": C.c_int64, "lpf_ppr_pack_workspace_bytes": C.c_int64,
-            "lpf_ppr_affected_workspace_bytes": C.c_int64, "lpf_ppr_splice_workspace_bytes": C.c_int64,
-            "lpf_gemm_tn_workspace_floats": C.c_int64, "lpf_layernorm_bwd_workspace_floats": C.c_int64,
-            "lpf_train_partial_blocks": C.c_int64, "lpf_pair_rows_piece_floats": C.c_int64,
-            "lpf_rank_shared_workspace_bytes": C.c_int64, "lpf_pair_walks_workspace_bytes": C.c_int64}
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lpformer_hip.h")
+HOST_NAMES = ("lpf_ppr_push_cpu", "lpf_ppr_push_cpu_sources", "lpf_host_free", "lpf_host_abi_version")  # liblpformer_host.so
 
 
 class LpfError(RuntimeError):
     pass
 
+
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+            "float": C.c_float, "double": C.c_double}
+_RETURNS = {"int": C.c_int, "int64_t": C.c_int64, "const char *": C.c_char_p, "void": None}
+_DECL = re.compile(r"([\w\s*]+?)\b(lpf_\w+)\s*\(([^()]*)\)\s*;")
+_PARAM = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*)*)(?:\b\w+)?")
+
+
+def _argtype(param, where):
+    m = _PARAM.fullmatch(param.strip())
+    base, stars = (m.group(1), m.group(2).count("*")) if m else (None, 0)
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 1:
+        return {"int": C.POINTER(C.c_int), "char": C.c_char_p}.get(base, C.c_void_p)
+    if stars == 2:
+        return C.POINTER(C.c_void_p)
+    raise LpfError(f"{where}: no ctypes type for the parameter {param.strip()!r}")
+
+
+def _const_value(expr, where):
+    """An integer expression of decimal literals (optional u suffix), parentheses, unary minus and <<."""
+    toks = re.findall(r"\d+[uU]?|<<|[()-]|\S", expr)
+    bad = LpfError(f"{where}: {expr.strip()!r} is not an integer expression")
+
+    def unary():
+        t = toks.pop(0) if toks else ""
+        if t == "-":
+            return -unary()
+        if t == "(":
+            v = shift()
+            if not toks or toks.pop(0) != ")":
+                raise bad
+            return v
+        if not t[:1].isdigit():
+            raise bad
+        return int(t.rstrip("uU"))
+
+    def shift():
+        v = unary()
+        while toks and toks[0] == "<<":
+            toks.pop(0)
+            v <<= unary()
+        return v
+
+    v = shift()
+    if toks:
+        raise bad
+    return v
+
+
+def parse_header(text):
+    """``(prototypes, constants)`` of a C header in the form of include/lpformer_hip.h: every ``ret lpf_name(params);``
+    as name -> (restype, [argtypes]) and every ``#define LPF_NAME value`` as name -> int.  Whatever it cannot read is an
+    LpfError, never skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants, code = {}, []
+    for line in text.split("\n"):
+        if not line.lstrip().startswith("#"):
+            code.append(line)
+            continue
+        m = re.match(r"\s*#\s*define\s+(LPF_\w+)(.*)", line)
+        if m:
+            if m.group(1) in constants:
+                raise LpfError(f"{m.group(1)} is defined twice")
+            constants[m.group(1)] = _const_value(m.group(2), m.group(1))
+    code = "\n".join(code)
+    prototypes = {}
+    for ret, name, params in _DECL.findall(code):
+        ret = " ".join(ret.replace("*", " * ").split())
+        if ret not in _RETURNS:
+            raise LpfError(f"{name}: no ctypes type for the return type {ret!r}")
+        if name in prototypes:
+            raise LpfError(f"{name} is declared twice")
+        params = [] if params.strip() == "void" else params.split(",")
+        prototypes[name] = (_RETURNS[ret], [_argtype(p, name) for p in params])
+    rest = _DECL.sub(" ", code)
+    if not re.fullmatch(r'\s*(extern\s*"C"\s*\{\s*\}\s*)?', rest):
+        raise LpfError(f"cannot read this part of the header: {' '.join(rest.split())[:200]!r}")
+    return prototypes, constants
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise LpfError(f"the C header was looked for at {HEADER_PATH} "
+                       f"(lpformer_amd runs from its source tree): {e}") from None
+
+
+# The header is the one place an entry point or an ABI constant is written: name -> (restype, [argtypes]) of every
+# declaration, LPF_NAME -> int of every #define.
+PROTOTYPES, CONST = _read_header()
+HOST_PROTOTYPES = {name: PROTOTYPES[name][1] for name in HOST_NAMES}
+HIP_PROTOTYPES = {name: args for name, (_, args) in PROTOTYPES.items() if name not in HOST_NAMES}
+
+ABI_VERSION = CONST["LPF_ABI_VERSION"]
+FLAG_RELU = CONST["LPF_FLAG_RELU"]
+SELECT_ERR_NODE_RANGE = CONST["LPF_SELECT_ERR_NODE_RANGE"]
+SELECT_ERR_ITEM_CAP = CONST["LPF_SELECT_ERR_ITEM_CAP"]
+SELECT_ERR_ENTRY_CAP = CONST["LPF_SELECT_ERR_ENTRY_CAP"]
+ROWS_PERM_LB_WORDS = CONST["LPF_ROWS_PERM_LB_WORDS"]
+SELECT4_BLOCK = CONST["LPF_SELECT4_BLOCK"]
 
 _hip = None
 _host = None
@@ -201,10 +168,9 @@ class _RecordingLib:
 
 
 def _bind(lib, protos):
-    for name, argtypes in protos.items():
+    for name in protos:
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPE.get(name, C.c_int)
+        fn.restype, fn.argtypes = PROTOTYPES[name]
     return lib
 
 

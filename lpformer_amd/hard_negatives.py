@@ -32,8 +32,8 @@ from .sources import as_pairs, node_ids, raw_stream, resolve
 
 HEURISTICS = ("cn", "aa", "ra", "ppr", "feat")
 TWOHOP_KINDS = ("cn", "aa", "ra")
-MAX_K = 1024                          # k / 2 + 1 <= LPF_TOPK_MAX_K and LPF_INTERLEAVE_MAX_KH (include/lpformer_hip.h)
-SPLIT_DEFAULT = 512                   # LPF_TWOHOP_SPLIT_DEFAULT
+MAX_K = min(_lib.CONST["LPF_TOPK_MAX_K"], _lib.CONST["LPF_INTERLEAVE_MAX_KH"])   # k / 2 + 1 must fit both
+SPLIT_DEFAULT = _lib.CONST["LPF_TWOHOP_SPLIT_DEFAULT"]
 WORKSPACE_BUDGET = 1 << 30            # bytes of dense two-hop state (24 bytes per node and resident workgroup)
 MAX_GROUPS = 512
 

@@ -441,7 +441,7 @@ class _SelectWorkspace:
     def __init__(self, device, bs: int):
         self.device, self.bs = device, bs
         self.plan_blocks = int(_lib.hip().lpf_select_plan_blocks(bs))
-        self.ctl = torch.zeros(16, dtype=torch.int64, device=device)  # LPF_SELECT_CTL_WORDS
+        self.ctl = torch.zeros(_lib.CONST["LPF_SELECT_CTL_WORDS"], dtype=torch.int64, device=device)
         self.desc = torch.empty(16 * max(bs, 1), dtype=torch.int64, device=device)
         self.offs = torch.empty(bs + 1, dtype=torch.int64, device=device)
         self.plan_lb = torch.zeros(self.plan_blocks + 1, dtype=torch.int64, device=device)
@@ -489,7 +489,7 @@ class _Select4Workspace:
 
     def __init__(self, device, bs: int):
         self.device, self.bs = device, bs
-        self.ctl = torch.zeros(32, dtype=torch.int64, device=device)  # LPF_SELECT4_CTL_WORDS
+        self.ctl = torch.zeros(_lib.CONST["LPF_SELECT4_CTL_WORDS"], dtype=torch.int64, device=device)
         self.pair_tab = torch.zeros(4 * max(bs, 1), dtype=torch.int32, device=device)
         self.blk_cnt = torch.zeros(2 * ((bs + _lib.SELECT4_BLOCK - 1) // _lib.SELECT4_BLOCK) + 2, dtype=torch.int32,
                                    device=device)   # {entries, pairs with entries} per block
@@ -535,7 +535,7 @@ class _Select4RegionsWorkspace(_SelectWorkspace):
     def __init__(self, device, bs: int):
         self.device, self.bs = device, bs
         nblk = (bs + _lib.SELECT4_BLOCK - 1) // _lib.SELECT4_BLOCK
-        self.ctl = torch.zeros(32, dtype=torch.int64, device=device)            # LPF_SELECT4_CTL_WORDS
+        self.ctl = torch.zeros(_lib.CONST["LPF_SELECT4_CTL_WORDS"], dtype=torch.int64, device=device)
         self.pair_tab = torch.zeros(4 * max(bs, 1), dtype=torch.int32, device=device)
         self.blk_cnt = torch.zeros(2 * nblk + 2, dtype=torch.int32, device=device)
         self.blk_types = torch.zeros(4 * nblk + 4, dtype=torch.int32, device=device)

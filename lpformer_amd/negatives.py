@@ -42,10 +42,10 @@ import torch
 from . import _lib, graph, sources
 from ._lib import check as _check_rc, ptr
 
-MAX_K = 1024                          # LPF_NEGATIVE_MAX_K
-MAX_DRAWS = 1 << 30                   # LPF_NEGATIVE_MAX_DRAWS
-ROW_DRAWS = 1 << 20                   # LPF_NEGATIVE_ROW_DRAWS_DEFAULT
-PAIR_DRAWS = 1 << 16                  # LPF_NEGATIVE_PAIR_DRAWS_DEFAULT
+MAX_K = _lib.CONST["LPF_NEGATIVE_MAX_K"]
+MAX_DRAWS = _lib.CONST["LPF_NEGATIVE_MAX_DRAWS"]
+ROW_DRAWS = _lib.CONST["LPF_NEGATIVE_ROW_DRAWS_DEFAULT"]
+PAIR_DRAWS = _lib.CONST["LPF_NEGATIVE_PAIR_DRAWS_DEFAULT"]
 G = 0x9E3779B97F4A7C15
 _M64 = (1 << 64) - 1
 

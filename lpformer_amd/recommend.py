@@ -26,7 +26,7 @@ from . import _lib, graph
 from ._lib import check, ptr
 from .sources import model_graphs, node_ids, raw_stream
 
-MAX_K = 1024                 # LPF_TOPK_MAX_K (include/lpformer_hip.h)
+MAX_K = _lib.CONST["LPF_TOPK_MAX_K"]
 CANDIDATE_MODES = ("ppr", "all", "2hop")
 
 

@@ -35,7 +35,7 @@ import torch
 from . import _lib, graph, sources
 from ._lib import check, ptr
 
-MAX_T = 32                                  # LPF_THRESH_MAX_T (include/lpformer_hip.h)
+MAX_T = _lib.CONST["LPF_THRESH_MAX_T"]
 DEFAULT_GRID = (0, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1)
 TYPE_NAMES = ("cn", "1-hop", ">1-hop")
 _ARGS = ("thresh_cn", "thresh_1hop", "thresh_non1hop")
