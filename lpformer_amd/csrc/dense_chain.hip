@@ -132,12 +132,6 @@ __device__ __forceinline__ void dc_mfma(f32x4 (&acc)[TPW], const f32x4 *lw, cons
     }
 }
 
-__device__ __forceinline__ float dc_quad_sum(float v) {  // sum over the 4 lanes (q = 0..3) that share a sample
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
 // this lane's raw input values of one stage: k-group g reads k = 16 g + 4 q + (0..3) of row a (and row b)
 template <int G, int MODE>
 __device__ __forceinline__ void dc_input_load(f32x4 (&a)[G], f32x4 (&b)[G], const DenseChainArgs &A, const float *xa,
@@ -290,7 +284,7 @@ __global__ __launch_bounds__(DC_THREADS, MINW) void dense_chain_kernel(const Den
             float s1 = 0.f;
 #pragma unroll
             for (int c = 0; c < TPW1; ++c) s1 += acc1[c][0] + acc1[c][1] + acc1[c][2] + acc1[c][3];
-            s1 = dc_quad_sum(s1);  // padded features are exactly 0 and add nothing
+            s1 = lpf_quad_sum(s1);  // padded features are exactly 0 and add nothing
             if (q == 0) *my_x = s1;
             __syncthreads();
             const float mean = (half == 0 ? s1 + *peer_x : *peer_x + s1) / (float)A.N1;  // same order in both waves
@@ -304,7 +298,7 @@ __global__ __launch_bounds__(DC_THREADS, MINW) void dense_chain_kernel(const Den
                     s2 += d * d;
                 }
             }
-            s2 = dc_quad_sum(s2);
+            s2 = lpf_quad_sum(s2);
             if (q == 0) *my_x = s2;
             __syncthreads();
             const float rstd = 1.0f / sqrtf((half == 0 ? s2 + *peer_x : *peer_x + s2) / (float)A.N1 + 1e-5f);
@@ -336,7 +330,7 @@ __global__ __launch_bounds__(DC_THREADS, MINW) void dense_chain_kernel(const Den
                     const f32x4 w = *reinterpret_cast<const f32x4 *>(A.w2p + fbase + 16 * c);  // zero-padded
                     d = fmaf(acc1[c][0], w[0], fmaf(acc1[c][1], w[1], fmaf(acc1[c][2], w[2], fmaf(acc1[c][3], w[3], d))));
                 }
-                d = dc_quad_sum(d);
+                d = lpf_quad_sum(d);
                 __syncthreads();  // (the LayerNorm exchange, if any, has been read by everyone)
                 if (q == 0) *my_x = d;
                 __syncthreads();

@@ -70,12 +70,6 @@ constexpr int GF_NB = LPF_GF_NB;  // neighbours of EACH row of a pair requested 
 template <int NT> constexpr int gf_per_cu() { return NT == 8 ? 1 : 2; }
 constexpr int GF_STAGE = 512;    // float4 per packed stage (pack_dense pads a stage to 512)
 
-__device__ __forceinline__ float gf_row_sum(float v) {   // over the four lanes (q) of a row
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
 __device__ __forceinline__ float gf_partner(float v) {   // the value lane ^ 1 holds (DPP quad_perm [1,0,3,2])
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));
 }
@@ -86,7 +80,7 @@ __device__ __forceinline__ void gf_layernorm(f32x4 (&y)[NT], const float *g, con
     float s = 0.f;
 #pragma unroll
     for (int c = 0; c < NT; ++c) s += (y[c][0] + y[c][1]) + (y[c][2] + y[c][3]);
-    const float mean = gf_row_sum(s) * inv_d;
+    const float mean = lpf_quad_sum(s) * inv_d;
     float s2 = 0.f;
 #pragma unroll
     for (int c = 0; c < NT; ++c)
@@ -95,7 +89,7 @@ __device__ __forceinline__ void gf_layernorm(f32x4 (&y)[NT], const float *g, con
             const float d = y[c][r] - mean;
             s2 = fmaf(d, d, s2);
         }
-    const float rstd = 1.0f / sqrtf(gf_row_sum(s2) * inv_d + 1e-5f);
+    const float rstd = 1.0f / sqrtf(lpf_quad_sum(s2) * inv_d + 1e-5f);
 #pragma unroll
     for (int c = 0; c < NT; ++c) {
         const f32x4 gg = *reinterpret_cast<const f32x4 *>(g + 16 * c + 4 * q);

@@ -72,6 +72,64 @@ __device__ __forceinline__ float lpf_group_max(float v) {
     return v;
 }
 
+// sum over the four lanes {l, l ^ 16, l ^ 32, l ^ 48}: the lanes that share a row / a sample in the MFMA tile layouts
+__device__ __forceinline__ float lpf_quad_sum(float v) {
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+// Sum over the G lanes of a group, the same bits in every lane: DPP butterflies inside a row of 16 lanes (quad
+// permutes, then the half-row and the row mirrored: after two steps a quad holds one value, so a mirror IS the xor
+// partner), one swizzle across the rows, one pair of lane reads across the halves -- no LDS round trip per step
+// (__shfl_xor compiles to ds_bpermute_b32: five dependent round trips per entry were a third of the flip kernel).
+template <int CTRL>
+__device__ __forceinline__ float lpf_dpp(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+template <int G>
+__device__ __forceinline__ float lpf_dpp_group_sum(float v) {
+    v += lpf_dpp<0xB1>(v);                   // quad_perm [1,0,3,2]
+    v += lpf_dpp<0x4E>(v);                   // quad_perm [2,3,0,1]
+    if constexpr (G >= 8) v += lpf_dpp<0x141>(v);    // row_half_mirror
+    if constexpr (G >= 16) v += lpf_dpp<0x140>(v);   // row_mirror
+    if constexpr (G >= 32)
+        v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401f));  // lane ^ 16
+    if constexpr (G >= 64) {
+        const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
+        const float b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
+        v = a + b;
+    }
+    return v;
+}
+
+// Workgroup barrier that orders LDS ONLY.  __syncthreads() is a workgroup-scope fence + barrier, and the fence makes the
+// compiler drain the vector-memory counter -- loads and stores included -- in front of every barrier: in select3's run
+// kernel that turned each of the item loop's thirteen barriers into a wait for whatever global reads were in flight
+// (in-kernel stamps: ~2 us per dependent round trip, seven of them per item), and behind a loop of global stores every
+// barrier waits out a store round trip.
+// INVARIANT of every kernel that calls this: no wavefront hands GLOBAL data to another wavefront of its workgroup
+// across this barrier.  What a workgroup does pass through global memory carries its own wait (pair_rows' pieces: wait
+// + flag) or leaves the workgroup through agent-scope atomics (select3, select4).  So the barrier only has to order
+// LDS, and the global loads, stores and atomics requested ahead stay in flight across it.
+__device__ __forceinline__ void lpf_lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// The reference's fp32 round trip fl32((fl32(fl32(p*t)+t)-t)/t) for t in {1, 2}: p*1, p*2, x/1 and x/2 are exact, only
+// the add and the subtract round -- op by op, never a fused multiply-add
+__device__ __forceinline__ float lpf_rt1(float p) {
+#pragma clang fp contract(off)
+    return __fsub_rn(__fadd_rn(p, 1.0f), 1.0f);
+}
+__device__ __forceinline__ float lpf_rt2(float p) {
+#pragma clang fp contract(off)
+    return 0.5f * __fsub_rn(__fadd_rn(p * 2.0f, 2.0f), 2.0f);
+}
+
+// 11-bit multiplicative hash of a node id (the 2,048-slot LDS tables of neg_sample.hip and twohop.hip)
+__device__ __forceinline__ uint32_t lpf_hash11(int32_t c) { return ((uint32_t)c * 2654435761u) >> 21; }
+
 // first index i in [lo, hi) with a[i] >= key (a sorted ascending); returns hi if none
 __device__ __forceinline__ int64_t lpf_lower_bound(const int32_t *__restrict__ a, int64_t lo, int64_t hi, int32_t key) {
     while (lo < hi) {

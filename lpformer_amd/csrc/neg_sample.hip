@@ -41,8 +41,7 @@ __device__ __forceinline__ uint64_t ns_key(uint64_t seed, uint64_t slot) { retur
 __device__ __forceinline__ int32_t ns_node(uint64_t key, uint64_t j, uint64_t n) {
     return (int32_t)__umul64hi(ns_mix64(key + NS_G * (j + 1)), n);
 }
-__device__ __forceinline__ uint32_t ns_hash(int32_t c) { return ((uint32_t)c * 2654435761u) >> 21; }   // 11 bits
-static_assert(NS_TABLE == 2048, "ns_hash yields 11 bits");
+static_assert(NS_TABLE == 2048, "lpf_hash11 yields 11 bits");
 
 struct RowArgs {
     int64_t R, n;
@@ -87,7 +86,7 @@ __global__ __launch_bounds__(LPF_WAVE) void negative_rows_kernel(RowArgs A) {
         const bool valid = j < max_draws && c != (int32_t)s && !lpf_sorted_has(A.col, r0, r1, c);
         uint32_t slot = 0;
         if (valid) {
-            slot = ns_hash(c);
+            slot = lpf_hash11(c);
             for (;;) {
                 const int32_t prev = atomicCAS(&keys[slot], -1, c);
                 if (prev == -1 || prev == c) break;

@@ -46,29 +46,6 @@ struct FlipArgs {
     int64_t units_cap;
 };
 
-// Sum over the G lanes of a group, the same bits in every lane: DPP butterflies inside a row of 16 lanes (quad
-// permutes, then the half-row and the row mirrored: after two steps a quad holds one value, so a mirror IS the xor
-// partner), one swizzle across the rows, one pair of lane reads across the halves -- no LDS round trip per step
-// (__shfl_xor compiles to ds_bpermute_b32: five dependent round trips per entry were a third of this kernel).
-template <int CTRL>
-__device__ __forceinline__ float fl_dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-template <int G>
-__device__ __forceinline__ float fl_group_sum(float v) {
-    v += fl_dpp<0xB1>(v);                   // quad_perm [1,0,3,2]
-    v += fl_dpp<0x4E>(v);                   // quad_perm [2,3,0,1]
-    if constexpr (G >= 8) v += fl_dpp<0x141>(v);    // row_half_mirror
-    if constexpr (G >= 16) v += fl_dpp<0x140>(v);   // row_mirror
-    if constexpr (G >= 32)
-        v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401f));  // lane ^ 16
-    if constexpr (G >= 64) {
-        const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-        const float b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-        v = a + b;
-    }
-    return v;
-}
 // 1 / sqrt(var + eps) of the hidden layer's LayerNorm (closed form, pe_common.h) with the hardware reciprocal square root
 __device__ __forceinline__ float fl_rstd(const PeStat &s, float x, float y) {
     const float var = s.c00 * x * x + s.c11 * y * y + s.cbb + 2.0f * (s.c01 * x * y + s.c0b * x + s.c1b * y);
@@ -324,7 +301,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_flip_kernel(cons
             const f32x2 y01 = x01 * 0.2f, y23 = x23 * 0.2f;
             const f32x2 l01 = {fmaxf(x01.x, y01.x), fmaxf(x01.y, y01.y)}, l23 = {fmaxf(x23.x, y23.x), fmaxf(x23.y, y23.y)};
             const f32x2 sp = l01 * at01 + l23 * at23;
-            const float s = fl_group_sum<G>(sp.x + sp.y);
+            const float s = lpf_dpp_group_sum<G>(sp.x + sp.y);
             if (on) {
                 if (i > 0 && pair_i != last_pair) {   // the previous entry closed a segment
                     flush(cur_pair, first ? st0 : true, true);

@@ -92,36 +92,7 @@ struct RowsArgs {
     float grid_ofs;
 };
 
-template <int CTRL>
-__device__ __forceinline__ float pr_dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-// sum over the G lanes of a group, the same bits in every lane (pair_flip.hip::fl_group_sum)
-template <int G>
-__device__ __forceinline__ float pr_group_sum(float v) {
-    v += pr_dpp<0xB1>(v);
-    v += pr_dpp<0x4E>(v);
-    if constexpr (G >= 8) v += pr_dpp<0x141>(v);
-    if constexpr (G >= 16) v += pr_dpp<0x140>(v);
-    if constexpr (G >= 32)
-        v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401f));
-    if constexpr (G >= 64) {
-        const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-        const float b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-        v = a + b;
-    }
-    return v;
-}
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// Workgroup barrier that orders LDS only.  __syncthreads() is a workgroup fence + barrier and the fence drains the
-// vector-memory counter: behind a loop of global stores (count features, constant rows, finished rows) every barrier of
-// the set-up would wait out a store round trip.  The wavefronts of a workgroup hand each other nothing through global
-// memory here except the pieces, which have their own wait + flag.
-__device__ __forceinline__ void pr_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 // (tuning builds, -DPR_STAMPS: wall-clock marks -- 100 MHz -- of lane 0 of every wavefront; tools/rows_stamps.py)
 #ifdef PR_STAMPS
@@ -527,14 +498,14 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
             y[v] = make_float4(o[v].a.x * inv + vb.x, o[v].a.y * inv + vb.y, o[v].b.x * inv + vb.z, o[v].b.y * inv + vb.w);
             sum += (y[v].x + y[v].y) + (y[v].z + y[v].w);
         }
-        const float mean = pr_group_sum<G>(sum) * (1.0f / (float)D);
+        const float mean = lpf_dpp_group_sum<G>(sum) * (1.0f / (float)D);
         float sq = 0.f;
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
             y[v] = make_float4(y[v].x - mean, y[v].y - mean, y[v].z - mean, y[v].w - mean);
             sq += (y[v].x * y[v].x + y[v].y * y[v].y) + (y[v].z * y[v].z + y[v].w * y[v].w);
         }
-        const float var = pr_group_sum<G>(sq) * (1.0f / (float)D);
+        const float var = lpf_dpp_group_sum<G>(sq) * (1.0f / (float)D);
         const float rstd = __builtin_amdgcn_rsqf(var + 1e-5f);
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
@@ -614,7 +585,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
                 e_pre[i] = A.pair_tab[c0 + (k < cn ? k : cn - 1)];
             }
         }
-        pr_lds_barrier();   // the previous chunk's lists and pointers are no longer needed
+        lpf_lds_barrier();   // the previous chunk's lists and pointers are no longer needed
         int64_t v0, v1;
         if constexpr (PT) {
             // ltp[k] = first entry, ltp[TPS + k] / ltp[2 TPS + k] = common neighbours / one-hop nodes of pair k, lcum = the
@@ -643,7 +614,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
             }
             if (lane == 63) lwcnt[wave] = x;
             if (tid < 4) lctl[tid] = 0;
-            pr_lds_barrier();
+            lpf_lds_barrier();
             int pre = 0, tot = 0;
             for (int w = 0; w < NTH / 64; ++w) {
                 if (w < wave) pre += lwcnt[w];
@@ -668,7 +639,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
             ltp[t * TPS + k] = (int)v;
         }
         if (tid < 4) lctl[tid] = 0;
-        pr_lds_barrier();
+        lpf_lds_barrier();
         // pair-major base of the chunk, then every pair's start relative to it (fits 31 bits: ent_cap does)
         v0 = (int64_t)ltp[0] + ltp[TPS] + ltp[2 * TPS];
         v1 = (int64_t)ltp[cn] + ltp[TPS + cn] + ltp[2 * TPS + cn];
@@ -683,7 +654,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
         const bool inl = n_units <= PR_FLAGS;
         if (inl)
             for (int k = tid; k < n_units; k += NTH) lflag[k] = 0;
-        pr_lds_barrier();
+        lpf_lds_barrier();
         PR_STAMP(2);
         PR_STAMP(3);
         // ---- the chunk's units: 16 consecutive entries of the pair-major order each, EPW of them per wavefront and
@@ -914,7 +885,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
                     if (v == 0) sp = l01 * at01[v] + l23 * at23[v];
                     else sp += l01 * at01[v] + l23 * at23[v];
                 }
-                const float s = pr_group_sum<G>(sp.x + sp.y);
+                const float s = lpf_dpp_group_sum<G>(sp.x + sp.y);
                 if (on) {
                     if (meta & 4) {          // first entry of a piece: fresh state
                         m = -INFINITY; l = 0.f;
@@ -1047,7 +1018,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
         }
         int n_multi = 0;
         if (lists) {
-            pr_lds_barrier();
+            lpf_lds_barrier();
             const int n_empty = lctl[0];
             n_multi = lctl[1];
             // ---- pairs without entries: the constant row
@@ -1100,7 +1071,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
     //      step stays bitwise the eager one.
     if (PT && A.perm && tid == 0 && blockIdx.x == gridDim.x - 1) *A.n_nonempty = (int64_t)lctl[10];
     if (A.perm) {
-        pr_lds_barrier();
+        lpf_lds_barrier();
         if (!PT && wave == 0) {   // (PT: the selection counted the pairs with entries per block -- known since the set-up)
             const uint32_t epoch = (uint32_t)lctl[11];
             const int64_t nb = blockIdx.x;
@@ -1131,7 +1102,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
                 }
             }
         }
-        pr_lds_barrier();
+        lpf_lds_barrier();
         int64_t ne_base = (int64_t)(uint32_t)lctl[8] | ((int64_t)lctl[9] << 32);   // pairs with entries in front
         for (int64_t k0 = P0; k0 < P1; k0 += NTH) {
             const int64_t k = k0 + tid;
@@ -1139,7 +1110,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
             const bool ne = in && nonempty(k);
             const uint64_t b_ne = __ballot(ne), b_all = __ballot(in);
             if (lane == 0) { lwcnt[wave] = __popcll(b_ne); lwcnt[16 + wave] = __popcll(b_all); }
-            pr_lds_barrier();
+            lpf_lds_barrier();
             int pre_ne = 0, pre_all = 0, tot_ne = 0;
             for (int w = 0; w < NTH / 64; ++w) {
                 if (w < wave) { pre_ne += lwcnt[w]; pre_all += lwcnt[16 + w]; }
@@ -1149,7 +1120,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
             const int r_ne = pre_ne + __popcll(b_ne & lt), r_all = pre_all + __popcll(b_all & lt);
             if (ne) A.perm[ne_base + r_ne] = (int32_t)k;
             else if (in) A.perm[A.bs - 1 - ((k0 - ne_base) + (r_all - r_ne))] = (int32_t)k;
-            pr_lds_barrier();
+            lpf_lds_barrier();
             ne_base += tot_ne;
         }
     }

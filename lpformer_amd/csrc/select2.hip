@@ -52,12 +52,6 @@ struct alignas(16) PairDesc {
 };
 static_assert(sizeof(PairDesc) == 128, "PairDesc is one 128-byte line");
 
-// fl32((fl32(fl32(p*t)+t)-t)/t) for t in {1,2}: p*1, p*2, x/1 and x/2 are exact, only the add and subtract round
-__device__ __forceinline__ float s2_round_trip(float p, bool two) {
-    if (two) return 0.5f * __fsub_rn(__fadd_rn(p * 2.0f, 2.0f), 2.0f);
-    return __fsub_rn(__fadd_rn(p, 1.0f), 1.0f);
-}
-
 // position of key in the sorted array a[0..n), or -1 (a in global memory or LDS).  Lower bound that remembers the
 // value under the final `hi`: when the loop ends lo == hi, and a[hi] was loaded the last time hi moved (or hi never
 // moved and lo == n), so no load is needed after the loop.  (hipcc 7.2 miscompiled the usual "if (lo < n &&
@@ -350,7 +344,7 @@ __device__ __forceinline__ bool s2_type_slot(const RunArgs &A, const RunLds &L, 
         own = own_in;
         if (cn) {
             other = A.selfp[d.rb0 + j];
-        } else if (s2_round_trip(own, false) >= A.th_1) {  // otherwise it is dropped anyway
+        } else if (lpf_rt1(own) >= A.th_1) {  // otherwise it is dropped anyway
             float v;
             if (s2_lookup_hashed(A.val_cv, from_a ? d.pb0 : d.pa0, from_a ? d.nPb : d.nPa, x, v)) other = v;
         }
@@ -358,14 +352,15 @@ __device__ __forceinline__ bool s2_type_slot(const RunArgs &A, const RunLds &L, 
         const int64_t m0 = from_a ? d.pa0 : d.pb0, v0 = from_a ? d.pb0 : d.pa0;
         const int im = s2_find(A.val_col + m0, from_a ? d.nPa : d.nPb, x);
         own = im >= 0 ? A.val_val[m0 + im] : 0.f;
-        if (cn || s2_round_trip(own, false) >= A.th_1) {
+        if (cn || lpf_rt1(own) >= A.th_1) {
             const int idx = s2_find(A.val_col + v0, from_a ? d.nPb : d.nPa, x);
             if (idx >= 0) other = A.val_val[v0 + idx];
         }
     }
     const bool two = cn && !A.mode_cn;   // (t = 2 for a common neighbour; mode "cn": t = 1, as in select3.hip)
-    const float pa = s2_round_trip(from_a ? own : other, two);
-    const float pb = s2_round_trip(from_a ? other : own, two);
+    const float ua = from_a ? own : other, ub = from_a ? other : own;
+    const float pa = two ? lpf_rt2(ua) : lpf_rt1(ua);
+    const float pb = two ? lpf_rt2(ub) : lpf_rt1(ub);
     const float th = cn ? A.th_cn : A.th_1;
     const bool keep = pa >= th && pb >= th && (cn || !A.mode_cn);
     code = keep ? (cn ? 1 : 2) : 0;

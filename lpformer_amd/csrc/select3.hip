@@ -171,16 +171,6 @@ struct RunLds3 {
 };
 static_assert(sizeof(RunLds3) <= 48 * 1024, "three workgroups per CU");
 
-// Workgroup barrier that orders LDS ONLY.  __syncthreads() is a workgroup-scope fence + barrier, and the fence makes the
-// compiler drain the vector-memory counter -- loads included -- in front of every barrier: in the run kernel that turned
-// each of the item loop's thirteen barriers into a wait for whatever global reads were in flight (in-kernel stamps: ~2 us
-// per dependent round trip, seven of them per item).  Nothing global is handed from one wavefront of a workgroup to
-// another here -- what leaves a workgroup for others goes through agent-scope atomics --, so the barriers only have to
-// order LDS, and the loads requested ahead (next item's ticket, window, descriptors) stay in flight across them.
-__device__ __forceinline__ void s3_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 // Entries of the parked item from L.pk to their final place, the segment starts of the pairs that begin in it and,
 // from the last item, the totals.  L.base holds the item's place per type.
 __device__ __forceinline__ void s3_write_out(const RunArgs3 &A, RunLds3 &L, int64_t bs, int tid) {
@@ -218,7 +208,7 @@ __device__ __forceinline__ void s3_write_out(const RunArgs3 &A, RunLds3 &L, int6
 // Write-out of the parked item, if there is one (whole workgroup; barriers at both ends).
 __device__ __forceinline__ void s3_finish_parked(const RunArgs3 &A, RunLds3 &L, uint32_t epoch, int64_t bs, int lane,
                                                  int wave, int tid) {
-    s3_lds_barrier();
+    lpf_lds_barrier();
     if (L.p_live) {
         if (wave < 3) {
 #ifdef S3_ABL_NOLB
@@ -229,10 +219,10 @@ __device__ __forceinline__ void s3_finish_parked(const RunArgs3 &A, RunLds3 &L, 
 #endif
             if (lane == 0) L.base[wave] = base;
         }
-        s3_lds_barrier();
+        lpf_lds_barrier();
         s3_write_out(A, L, bs, tid);
     }
-    s3_lds_barrier();
+    lpf_lds_barrier();
 }
 
 // (tuning builds, -DS3_STAMPS: where does an item's time go?  Thread 0 of every workgroup accumulates the wall-clock
@@ -274,7 +264,7 @@ __global__ __launch_bounds__(S3_THREADS, S3_MIN_WAVES) void select3_run_kernel(c
         L.nx_pf = t < n_items ? A.item_pair[t] : 0;
     }
     if (tid < 2 * S3_GROUPS) L.bits[tid] = 0u;
-    s3_lds_barrier();
+    lpf_lds_barrier();
     // An item's window (slot offsets of its pairs) and its first S3_DESC_AHEAD descriptors (one int4 per thread; an item
     // of 1,024 slots rarely holds more pairs) are REQUESTED as soon as the item is known -- for the first item here, for
     // every other one behind the typing of the item before it -- and consumed at the top of the loop: they travel while
@@ -310,7 +300,7 @@ __global__ __launch_bounds__(S3_THREADS, S3_MIN_WAVES) void select3_run_kernel(c
         const int n_here = cur.n_here, n4a = cur.n4a;
         const int4 dreg = cur.dreg;
         int64_t v = cur.v;
-        s3_lds_barrier();  // the previous item's window is no longer needed (and its bit map is zero again)
+        lpf_lds_barrier();  // the previous item's window is no longer needed (and its bit map is zero again)
         S3_STAMP(1);    // top barrier (waits for the slowest wavefront of the previous item)
         if (it >= n_items) break;
         int64_t nx_t = 0;
@@ -329,9 +319,9 @@ __global__ __launch_bounds__(S3_THREADS, S3_MIN_WAVES) void select3_run_kernel(c
             const int cntp = __popcll(__ballot(in));
             if (lane == 0) L.pre[wave] = cntp;       // (scratch: two partial counts)
         }
-        s3_lds_barrier();
+        lpf_lds_barrier();
         const int np = L.pre[0] + L.pre[1];  // pairs with at least one slot in this item (>= 1)
-        s3_lds_barrier();
+        lpf_lds_barrier();
         S3_STAMP(3);    // window processed
         if (tid < S3_GROUPS) {               // exclusive popcount scan over the 64-slot groups
             int s = 0;
@@ -347,7 +337,7 @@ __global__ __launch_bounds__(S3_THREADS, S3_MIN_WAVES) void select3_run_kernel(c
         // the next item's first pair: requested now, in flight beside this item's walked entries
         int64_t nx_p = 0;
         if (drawer && nx_t < n_items) nx_p = A.item_pair[nx_t];
-        s3_lds_barrier();
+        lpf_lds_barrier();
         S3_STAMP(4);    // rest of the descriptors + barrier
 
         // ---- typing: one slot per thread and round; everything a kept slot needs later stays in registers.  The rounds
@@ -413,7 +403,7 @@ __global__ __launch_bounds__(S3_THREADS, S3_MIN_WAVES) void select3_run_kernel(c
             if (i < np * 2 * (S3_MINI_WORDS / 4)) (&L.flt[0][0][0])[i] = fr[f];
         }
         if (drawer) { L.nx_ticket = nx_t; L.nx_pf = nx_p; }   // (read behind the typing barrier below)
-        s3_lds_barrier();
+        lpf_lds_barrier();
         S3_STAMP_WAIT(5);   // walked entries and mini filters arrived
         int4 bv[S3_ROUNDS][S3_BUCKET / 2];
 #pragma unroll
@@ -452,7 +442,7 @@ __global__ __launch_bounds__(S3_THREADS, S3_MIN_WAVES) void select3_run_kernel(c
                 c[0] = __popcll(b0); c[1] = __popcll(b1); c[2] = __popcll(b2);
             }
         }
-        s3_lds_barrier();
+        lpf_lds_barrier();
         S3_STAMP(8);    // arithmetic + ballots + barrier
         // the bit map was read by the typing above only; the next item (drawn meanwhile) is requested now
         if (tid < 2 * S3_GROUPS) L.bits[tid] = 0u;
@@ -486,7 +476,7 @@ __global__ __launch_bounds__(S3_THREADS, S3_MIN_WAVES) void select3_run_kernel(c
             L.p_live = 1;
         }
         if (tid < S3_PAIRS) L.ps[tid][3] = 0;
-        s3_lds_barrier();
+        lpf_lds_barrier();
 #pragma unroll
         for (int r = 0; r < S3_ROUNDS; ++r) {
             const int g = S3_WAVES * r + wave;

@@ -78,13 +78,6 @@ struct Lds4 {
     int32_t run, ovf;
 };
 
-// Workgroup barrier that orders LDS only (select3.hip: __syncthreads() would drain the vector-memory counter -- here
-// the allocation atomic of wavefront 0 and the loads requested ahead stay in flight across it).  Nothing global is
-// handed between the wavefronts of a workgroup.
-__device__ __forceinline__ void s4_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 // (tuning builds, -DS4_STAMPS: thread 0 of every workgroup leaves the wall clock -- 100 MHz -- at the marks below in a
 //  debug buffer; tools/select4_stamps.py)
 #ifdef S4_STAMPS
@@ -165,7 +158,7 @@ __global__ __launch_bounds__(NTH, 4) void select4_kernel(const Args4 A) {
         if (i < FP) (&L.flt[0][0][0])[i] = fr[f];
     }
     S4_STAMP(1);    // plan issued (wavefront 0: ids -> node records -> descriptors; the others: ids -> filter pieces)
-    s4_lds_barrier();
+    lpf_lds_barrier();
     S4_STAMP(2);    // plan barrier
     // the blocks' slots one after the other: lane j holds the first slot of pair j of every block
     int off[NB], myloc[NB], S = 0;
@@ -186,7 +179,7 @@ __global__ __launch_bounds__(NTH, 4) void select4_kernel(const Args4 A) {
     volatile int32_t *const sfw = &L.sflag[wave][0][0];
 
     for (int s0 = 0; s0 < S; s0 += NTH * S4_ROUNDS) {
-        if (s0 > 0) s4_lds_barrier();   // (the previous batch's round offsets are no longer needed)
+        if (s0 > 0) lpf_lds_barrier();   // (the previous batch's round offsets are no longer needed)
         // ---- typing: one slot per thread and round; the rounds are taken together, phase by phase, so that their memory
         //      round trips overlap -- every round's walked entry, then every round's bucket, then the arithmetic
         int code[S4_ROUNDS], node[S4_ROUNDS], win[S4_ROUNDS];
@@ -271,7 +264,7 @@ __global__ __launch_bounds__(NTH, 4) void select4_kernel(const Args4 A) {
             if (lane == 0) L.rcnt[g] = __popcll(keptb[r]);
         }
         if (s0 == 0) S4_STAMP(5);         // arithmetic + ballots
-        s4_lds_barrier();
+        lpf_lds_barrier();
         if (s0 == 0) S4_STAMP(6);         // typing barrier
         // ---- the rounds' places inside the block: one scan over the rounds of the batch (wavefront 0)
         if (wave == 0) {
@@ -290,7 +283,7 @@ __global__ __launch_bounds__(NTH, 4) void select4_kernel(const Args4 A) {
                 L.ovf = base_reg + ((S + 7) & ~7) > shard_cap ? 1 : 0;
             }
         }
-        s4_lds_barrier();
+        lpf_lds_barrier();
         if (s0 == 0) S4_STAMP(7);         // scan + barrier
         const int64_t base = L.base;
         const bool ovf = L.ovf != 0;
@@ -307,7 +300,7 @@ __global__ __launch_bounds__(NTH, 4) void select4_kernel(const Args4 A) {
         }
     }
     S4_STAMP(8);    // entries written (issued), further batches
-    s4_lds_barrier();
+    lpf_lds_barrier();
     S4_STAMP(9);
     const bool ovf = S > 0 && L.ovf != 0;
     if (wave < NB) {    // block q's {entries, pairs with entries}: lane = pair

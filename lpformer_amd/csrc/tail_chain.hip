@@ -120,12 +120,6 @@ __device__ __forceinline__ void tc_mfma(f32x4 (&acc)[TPW], const uint2 *lw, cons
     }
 }
 
-__device__ __forceinline__ float tc_quad_sum(float v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
 // LayerNorm over the n real features held by the wave pair (this wave: TPW tiles from feature fbase), in place
 template <int TPW>
 __device__ __forceinline__ void tc_layernorm(f32x4 (&acc)[TPW], int fbase, int n, const float *g, const float *b, int half,
@@ -133,7 +127,7 @@ __device__ __forceinline__ void tc_layernorm(f32x4 (&acc)[TPW], int fbase, int n
     float s1 = 0.f;
 #pragma unroll
     for (int c = 0; c < TPW; ++c) s1 += acc[c][0] + acc[c][1] + acc[c][2] + acc[c][3];
-    s1 = tc_quad_sum(s1);  // padded features are exactly 0 and add nothing
+    s1 = lpf_quad_sum(s1);  // padded features are exactly 0 and add nothing
     __syncthreads();       // exchange slots free
     if (q == 0) *my_x = s1;
     __syncthreads();
@@ -146,7 +140,7 @@ __device__ __forceinline__ void tc_layernorm(f32x4 (&acc)[TPW], int fbase, int n
             const float d = (fbase + 16 * c + r < n) ? acc[c][r] - mean : 0.f;
             s2 += d * d;
         }
-    s2 = tc_quad_sum(s2);
+    s2 = lpf_quad_sum(s2);
     __syncthreads();
     if (q == 0) *my_x = s2;
     __syncthreads();
@@ -263,7 +257,7 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
 #pragma unroll
                 for (int r = 0; r < 4; ++r) d = fmaf(fmaxf(acc[c][r] + b[r], 0.f), w[r], d);
             }
-            d = tc_quad_sum(d);
+            d = lpf_quad_sum(d);
             if (q == 0) *my_x = d;
             __syncthreads();
             if (live && q == 0 && half == 0) {
@@ -498,7 +492,7 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
 #pragma unroll
             for (int r = 0; r < 4; ++r) d = fmaf(fmaxf(accC[c][r] + b[r], 0.f), w[r], d);
         }
-        d = tc_quad_sum(d);
+        d = lpf_quad_sum(d);
         __syncthreads();  // exchange slots free (the LayerNorm exchanges have been read by everyone)
         if (q == 0) *my_x = d;
         __syncthreads();

@@ -7,7 +7,7 @@
 //   type 0  v in N(a) & N(b)                                   ra = rt2(P[a,v]), rb = rt2(P[b,v])   (mode "cn": rt1)
 //   type 1  v in exactly one of N(a), N(b)                     ra = rt1(P[a,v]), rb = rt1(P[b,v])
 //   type 2  v in neither, P[a,v] > 0 and P[b,v] > 0 (stored)   ra = rt1(P[a,v]), rb = rt1(P[b,v])
-// (walk::rt1 / rt2: the reference's fp32 round trips, op by op) and count[p, t, j] = #{v of type t: ra >= theta_j and
+// (lpf_rt1 / lpf_rt2: the reference's fp32 round trips, op by op) and count[p, t, j] = #{v of type t: ra >= theta_j and
 // rb >= theta_j}: exactly what a model built with that threshold selects, boundary values included.  No special case
 // for v in {a, b} or a == b.  Mode "cn" has type 0 only.
 //
@@ -124,8 +124,8 @@ __device__ __forceinline__ int slot_type(const ProfArgs &A, const PairWalk &w, i
         vb = src_a ? wo : ws;
     }
     const bool two = type == 0 && !A.mode_cn;
-    const float ra = two ? walk::rt2(va) : walk::rt1(va);
-    const float rb = two ? walk::rt2(vb) : walk::rt1(vb);
+    const float ra = two ? lpf_rt2(va) : lpf_rt1(va);
+    const float rb = two ? lpf_rt2(vb) : lpf_rt1(vb);
     for (int j = 0; j < A.T; ++j) k += (ra >= th[j] && rb >= th[j]) ? 1 : 0;   // (LDS broadcast reads)
     return type;
 }

@@ -404,15 +404,14 @@ struct ILArgs {
     int32_t *n_ranked;                          // [U]
 };
 
-__device__ __forceinline__ uint32_t il_hash(int32_t c) { return ((uint32_t)c * 2654435761u) >> 21; }   // 11 bits
-static_assert(IL_TABLE == 2048, "il_hash yields 11 bits");
+static_assert(IL_TABLE == 2048, "lpf_hash11 yields 11 bits");
 
 // Whether this lane's sequence element (id, index t; `ex`: it exists) is the first holder of its id.  Workgroup-uniform
 // call (one wavefront per workgroup).
 __device__ __forceinline__ bool il_claim(int32_t *keys, int32_t *tmin, int32_t id, int32_t t, bool ex) {
     uint32_t slot = 0;
     if (ex) {
-        slot = il_hash(id);
+        slot = lpf_hash11(id);
         for (;;) {
             const int32_t prev = atomicCAS(&keys[slot], -1, id);
             if (prev == -1 || prev == id) break;

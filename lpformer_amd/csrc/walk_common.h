@@ -50,10 +50,6 @@ __device__ __forceinline__ uint32_t bloom_hash(uint32_t v) {
     return h ^ (h >> 13);
 }
 
-// fl32((fl32(fl32(p*t)+t)-t)/t) for t in {1,2}: p*1, p*2, x/1 and x/2 are exact, only the add and subtract round
-__device__ __forceinline__ float rt1(float p) { return __fsub_rn(__fadd_rn(p, 1.0f), 1.0f); }
-__device__ __forceinline__ float rt2(float p) { return 0.5f * __fsub_rn(__fadd_rn(p * 2.0f, 2.0f), 2.0f); }
-
 // The three walks of pair (a, b) from the endpoints' node records (the plan of DESIGN.md 5.2): walk 0 / 1 = the nodes
 // that are neighbours of a / b, walk 2 = the >1-hop candidates.  `d` must be zero on entry.
 __device__ __forceinline__ void build_desc(PairDesc3 &d, int64_t a, int64_t b, const NodeRec (&r)[2], const int2 *adj_cv,
@@ -129,8 +125,8 @@ __device__ __forceinline__ Typed type_slot(int32_t x, float ws, int kindw, const
     const bool far = kind == K_T0 && found && !adj;
     // the reference's round trips (t = 2 for a common neighbour, 1 otherwise; mode "cn": 1)
     const bool two = cn && !mode_cn;
-    const float rs = two ? rt2(ws) : rt1(ws);
-    const float rl = two ? rt2(lv) : rt1(lv);
+    const float rs = two ? lpf_rt2(ws) : lpf_rt1(ws);
+    const float rl = two ? lpf_rt2(lv) : lpf_rt1(lv);
     int c = 0;
     if (cn) c = (rs >= th_cn && rl >= th_cn) ? 1 : 0;
     else if (hop) c = (!mode_cn && rs >= th_1 && rl >= th_1) ? 2 : 0;

@@ -30,7 +30,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib, graph, sources
+from . import _lib, graph, ops, sources
 from ._lib import check, ptr
 
 # half-open [lo, hi) cells for evaluate.metrics_by_bin / explain.attention_profile:
@@ -159,7 +159,7 @@ def pair_distance(source, edges, *, test_set: bool = False, max_dist=None, ignor
         nbytes = int(hip.lpf_pair_bfs_workspace_bytes(adj.n, n_groups))
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
         scratch = torch.empty(m_max + 1, dtype=torch.int32, device=dev)
-        st = sources.raw_stream(dev)
+        st = ops.raw_stream(dev)
         for lo, m in sources.chunks(P, chunk):
             check(hip.lpf_pair_bfs(m, adj.n, batch.data_ptr() + lo * 8, P, ptr(adj.rowptr),
                                    ptr(adj.col), 0 if max_dist is None else max_dist, 1 if ignore_direct else 0,

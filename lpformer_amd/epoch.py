@@ -22,7 +22,7 @@ from typing import Callable, Optional
 
 import torch
 
-from . import _lib, evaluate, graph, sources
+from . import _lib, evaluate, graph, ops
 from ._lib import check, ptr
 
 _CACHE_KEY = "_lpf_train_edges"          # data[...] = (the train_pos object it was built from, TrainEdges)
@@ -115,7 +115,7 @@ class TrainEdges:
             with torch.cuda.device(self.device):
                 check(_lib.hip().lpf_batch_cover(ptr(self.gid), ptr(self.mult), ptr(self.train_pos), E, G, ptr(p), B,
                                                  ptr(self.cnt), ptr(out), ptr(self._stats),
-                                                 sources.raw_stream(self.device)), "lpf_batch_cover")
+                                                 ops.raw_stream(self.device)), "lpf_batch_cover")
             return out
         # the same three phases in torch (CPU tensors): count, emit, reset
         ok = (p >= 0) & (p < E)

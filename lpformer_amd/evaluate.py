@@ -19,7 +19,8 @@ from typing import Optional
 
 import torch
 
-from .sources import as_pairs, raw_stream
+from .ops import raw_stream
+from .sources import as_pairs
 
 
 def _as_2xp(edges) -> torch.Tensor:

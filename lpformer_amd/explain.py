@@ -22,7 +22,8 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from .evaluate import CN_BINS
-from .sources import as_pairs, node_ids, raw_stream
+from .ops import f32_rows, raw_stream
+from .sources import as_pairs, node_ids
 
 MAX_TOP = 32
 TYPE_NAMES = ("padding", "cn", "1-hop", ">1-hop")     # values of ``types``
@@ -213,7 +214,7 @@ def explain(model, edges, top: int = 8, *, test_set: bool = False, adj_mask=None
         for lo in range(0, total, int(batch_size)):
             b = model._prep_batch(batch[:, lo:lo + int(batch_size)])
             bs = b.shape[1]
-            s, score, _, _ = model._pair_scores(b, _f32_rows(h), test_set, adj_mask)
+            s, score, _, _ = model._pair_scores(b, f32_rows(h), test_set, adj_mask)
             tp = s["type_ptr"][:3 * (bs + 1)].view(3, bs + 1)
             cap = min(s["cap"], s["sel_node"].numel(), s["sel_pa"].numel(), s["sel_pb"].numel(), score.numel())
             red = _reduce_device(tp, s["sel_node"], s["sel_pa"], s["sel_pb"], score, top, want_all, cap)
@@ -250,11 +251,6 @@ def explain(model, edges, top: int = 8, *, test_set: bool = False, adj_mask=None
                     torch.cat([l[3] for l in lists]))
         return Explanation(cat("nodes"), cat("weights"), cat("types"), cat("ppr_a"), cat("ppr_b"), torch.cat(counts),
                            cat("mass"), cat("entropy"), torch.cat(scores) if score_func is not None else None, full)
-
-
-def _f32_rows(x: torch.Tensor) -> torch.Tensor:
-    from .link_transformer import _as_f32_rows
-    return _as_f32_rows(x)
 
 
 def pairs_of(sources, rec):

@@ -19,7 +19,7 @@ import numpy as np
 import scipy.sparse as sp
 import torch
 
-from . import _lib
+from . import _lib, ops
 
 
 @dataclass
@@ -279,7 +279,7 @@ def gcn_norm_device(struct: DeviceCSR, stream=None) -> DeviceCSR:
     dev = struct.rowptr.device
     w_out = torch.empty(struct.nnz, dtype=torch.float32, device=dev)
     dis = torch.empty(struct.n, dtype=torch.float32, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    st = ops.raw_stream(dev) if stream is None else stream
     _lib.check(_lib.hip().lpf_gcn_norm_csr(struct.n, _lib.ptr(struct.rowptr), _lib.ptr(struct.col),
                                             _lib.ptr(struct.val), _lib.ptr(w_out), _lib.ptr(dis), st),
                "lpf_gcn_norm_csr")
@@ -293,7 +293,7 @@ def ppr_filter_device(ppr: DeviceCSR, mode: int, theta: float) -> DeviceCSR:
     (device twin of ``prefilter_nonhop`` / ``prefilter_onehop``)."""
     from . import _lib
     lib, dev, n = _lib.hip(), ppr.rowptr.device, ppr.n
-    st = torch.cuda.current_stream(dev).cuda_stream
+    st = ops.raw_stream(dev)
     lens = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
     _lib.check(lib.lpf_ppr_filter_count(n, _lib.ptr(ppr.rowptr), _lib.ptr(ppr.val), mode, float(theta),
                                         _lib.ptr(lens), st), "lpf_ppr_filter_count")
@@ -343,7 +343,7 @@ def ppr_filter_device_blocked(ppr: DeviceCSR, mode: int, theta: float) -> Blocke
     """T0 (mode 0) / P1 (mode 1) index of a device-resident PPR matrix in the blocked layout (same kept entries, same
     order as ``ppr_filter_device``; ``lpf_ppr_filter_count`` / ``_fill`` with padded row starts)."""
     lib, dev, n = _lib.hip(), ppr.rowptr.device, ppr.n
-    st = torch.cuda.current_stream(dev).cuda_stream
+    st = ops.raw_stream(dev)
     lens = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
     _lib.check(lib.lpf_ppr_filter_count(n, _lib.ptr(ppr.rowptr), _lib.ptr(ppr.val), mode, float(theta),
                                         _lib.ptr(lens), st), "lpf_ppr_filter_count")
@@ -482,7 +482,7 @@ def self_ppr_device(adj: DeviceCSR, ppr: DeviceCSR) -> torch.Tensor:
     out = torch.empty(max(adj.nnz, 1), dtype=torch.float32, device=dev)
     _lib.check(_lib.hip().lpf_self_ppr(adj.n, _lib.ptr(adj.rowptr), _lib.ptr(adj.col), _lib.ptr(ppr.rowptr),
                                        _lib.ptr(ppr.col), _lib.ptr(ppr.val), _lib.ptr(out),
-                                       torch.cuda.current_stream(dev).cuda_stream), "lpf_self_ppr")
+                                       ops.raw_stream(dev)), "lpf_self_ppr")
     return out[:adj.nnz]
 
 

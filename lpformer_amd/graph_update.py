@@ -37,7 +37,7 @@ import torch
 from . import _lib, graph
 from .graph import CSR, DeviceCSR
 from .ppr import calc_ppr, calc_ppr_gpu
-from .sources import raw_stream
+from .ops import raw_stream
 
 # Flagged share of the sources above which the ordinary full producer runs instead (same result by definition: a speed
 # knob).  Measured on the MI355X (tools/graph_update_timing.py, profiles/graph_update_timing.json, table in DESIGN 5.11):

@@ -28,7 +28,8 @@ import torch
 from . import _lib, graph, heuristics
 from ._lib import check, ptr
 from .recommend import plan_chunks, segment_topk
-from .sources import as_pairs, node_ids, raw_stream, resolve
+from .ops import raw_stream
+from .sources import as_pairs, node_ids, resolve
 
 HEURISTICS = ("cn", "aa", "ra", "ppr", "feat")
 TWOHOP_KINDS = ("cn", "aa", "ra")

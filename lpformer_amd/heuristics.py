@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, graph, sources
+from . import _lib, graph, ops, sources
 from ._lib import check, ptr
 
 KINDS = ("cn", "aa", "ra", "ppr", "feat")
@@ -81,7 +81,7 @@ def pair_heuristics(source, edges, *, test_set: bool = False, kinds=("cn", "aa",
     P = batch.shape[1]
     out = {}
     with torch.cuda.device(dev):
-        st = sources.raw_stream(dev)
+        st = ops.raw_stream(dev)
         want = [k for k in ("cn", "aa", "ra") if k in kinds]
         if want:
             cn = torch.empty(P, dtype=torch.int32, device=dev) if "cn" in want else None

@@ -35,7 +35,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, distance, graph, sources
+from . import _lib, distance, graph, ops, sources
 from ._lib import check, ptr
 
 MAX_LEN = 4                           # lpf_pair_walks: 1 <= max_len <= 4 (length 5 needs three-hop rows)
@@ -280,7 +280,7 @@ def pair_walks(source, edges, *, test_set: bool = False, max_len=3, ignore_direc
         n_groups = int(groups) if groups is not None else default_groups(adj.n, m_max, workspace_mb)
         nbytes = int(hip.lpf_pair_walks_workspace_bytes(adj.n, n_groups))
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        st = sources.raw_stream(dev)
+        st = ops.raw_stream(dev)
         for lo, m in sources.chunks(P, chunk):
             pairs, unit_ptr, order = _units(adj, batch[0, lo:lo + m], batch[1, lo:lo + m], bool(ignore_direct))
             part = torch.empty((m, L), dtype=torch.int64, device=dev)

@@ -21,16 +21,11 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, fold, graph, mask_delta, patterns
+from . import _lib, fold, graph, mask_delta, ops, patterns
 from . import dist as lpf_dist
 from ._lib import FLAG_RELU, check, ptr
+from .ops import f32_rows, gemm, layernorm_, pad4, raw_stream
 from .profile import KernelTimer
-
-
-def _stream(device):
-    """Raw hipStream_t of torch's current stream on ``device`` (the stream every C-ABI launch goes to)."""
-    idx = device.index if isinstance(device, torch.device) and device.index is not None else torch.cuda.current_device()
-    return torch._C._cuda_getCurrentRawStream(idx)
 
 
 def _on_device(fn):
@@ -58,50 +53,6 @@ def _require_gpu(t: torch.Tensor, what: str):
                             "lpformer_amd has no CPU fallback")
 
 
-def _pad4(k: int) -> int:
-    return (k + 3) & ~3
-
-
-def _as_f32_rows(x: torch.Tensor) -> torch.Tensor:
-    """fp32, 2-D, unit inner stride, 16-byte aligned rows (ld % 4 == 0); copies only when needed."""
-    if x.dtype != torch.float32:
-        x = x.float()
-    if x.dim() != 2:
-        x = x.reshape(-1, x.shape[-1])
-    if x.stride(1) != 1 or x.stride(0) % 4 != 0 or x.data_ptr() % 16 != 0 or x.stride(0) < x.shape[1]:
-        k = x.shape[1]
-        buf = torch.zeros(x.shape[0], _pad4(k), dtype=torch.float32, device=x.device)
-        buf[:, :k] = x
-        x = buf[:, :k]
-    return x
-
-
-# ------------------------------------------------------------------------------------------ kernels wrappers
-def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, addend=None, relu=False, out=None,
-         tag="gemm") -> torch.Tensor:
-    """out = a @ w.T (+bias) (+addend) (ReLU) through ``lpf_gemm_f32``.  ``a``/``w`` rows must be 16-byte aligned."""
-    _require_gpu(a, "gemm")
-    m, k = a.shape
-    n = w.shape[0]
-    assert w.shape[1] == k, (a.shape, w.shape)
-    if out is None:
-        out = torch.empty(m, n, dtype=torch.float32, device=a.device)
-    with KernelTimer.span(tag):
-        check(_lib.hip().lpf_gemm_f32(m, n, k, ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(addend),
-                                      0 if addend is None else addend.stride(0), ptr(out), out.stride(0),
-                                      FLAG_RELU if relu else 0, _stream(a.device)), "lpf_gemm_f32")
-    return out
-
-
-def layernorm_(x: torch.Tensor, g, b, relu=False, out=None) -> torch.Tensor:
-    out = x if out is None else out
-    with KernelTimer.span("layernorm"):
-        check(_lib.hip().lpf_layernorm_f32(x.shape[0], x.shape[1], ptr(x), x.stride(0), ptr(g), ptr(b), ptr(out),
-                                           out.stride(0), FLAG_RELU if relu else 0, _stream(x.device)),
-              "lpf_layernorm_f32")
-    return out
-
-
 class _PaddedLinear:
     """fp32 weight with rows padded to a multiple of 4 floats (what lpf_gemm_f32 wants), refreshed when the
     parameter changes."""
@@ -115,7 +66,7 @@ class _PaddedLinear:
         if key != self._key:
             w = weight.detach()
             if w.dtype != torch.float32 or w.shape[1] % 4 or not w.is_contiguous() or w.data_ptr() % 16:
-                buf = torch.zeros(w.shape[0], _pad4(w.shape[1]), dtype=torch.float32, device=w.device)
+                buf = torch.zeros(w.shape[0], pad4(w.shape[1]), dtype=torch.float32, device=w.device)
                 buf[:, :w.shape[1]] = w
                 w = buf[:, :weight.shape[1]]
             self._w, self._key = w, key
@@ -220,7 +171,7 @@ class DenseChain:
                 x.shape[0] if in_mode else 0, k1,
                 ptr(t["w1p"]), n1, ptr(t["b1"]), ptr(addend), 0 if addend is None else addend.stride(0),
                 ptr(t.get("ln_g")), ptr(t.get("ln_b")), FLAG_RELU if relu else 0, ptr(t.get("w2p")), n2,
-                ptr(t.get("b2")), o, ldo, pr, *extra, _stream(dev)), name)
+                ptr(t.get("b2")), o, ldo, pr, *extra, raw_stream(dev)), name)
         return res
 
 
@@ -260,32 +211,29 @@ class MLP(nn.Module):
             if y is not None:
                 return y
         if in_mode:
-            d = x.shape[1]
-            gathered = torch.empty(batch.shape[1], d, dtype=torch.float32, device=x.device)
-            args = (ptr(gathered), d, None, 0) if in_mode == 1 else (None, 0, ptr(gathered), d)
-            with KernelTimer.span("pair_gather"):
-                check(_lib.hip().lpf_pair_gather_f32(batch.shape[1], d, ptr(batch), batch.stride(0), x.shape[0], ptr(x),
-                                                     x.stride(0), *args, _stream(x.device)), "lpf_pair_gather_f32")
+            gathered = torch.empty(batch.shape[1], x.shape[1], dtype=torch.float32, device=x.device)
+            ops.pair_gather(x, batch, product=gathered if in_mode == 1 else None, sum=gathered if in_mode != 1 else None,
+                            tag="pair_gather")
             x = gathered
         h = x
         for i, lin in enumerate(self.linears[:-1]):
             w = self._pads[i].get(lin.weight)
-            hid = torch.empty(h.shape[0], _pad4(w.shape[0]), dtype=torch.float32, device=h.device)[:, :w.shape[0]]
-            gemm(h, w, lin.bias, out=hid)
+            hid = torch.empty(h.shape[0], pad4(w.shape[0]), dtype=torch.float32, device=h.device)[:, :w.shape[0]]
+            gemm(h, w, lin.bias, out=hid, tag="gemm")
             if self.norm is not None:
-                layernorm_(hid, self.norm.weight, self.norm.bias, relu=True)
+                layernorm_(hid, self.norm.weight, self.norm.bias, relu=True, tag="layernorm")
             else:
-                layernorm_(hid, None, None, relu=True)
+                layernorm_(hid, None, None, relu=True, tag="layernorm")
             h = hid
         last = self.linears[-1]
-        y = gemm(h, self._pads[-1].get(last.weight), last.bias, out=out)
+        y = gemm(h, self._pads[-1].get(last.weight), last.bias, out=out, tag="gemm")
         return y
 
     def forward(self, x):
         _require_gpu(x, "MLP.forward")
         with torch.no_grad():
             lead = x.shape[:-1]
-            y = self.run(_as_f32_rows(x))
+            y = self.run(f32_rows(x))
             y = y.reshape(*lead, y.shape[-1]).squeeze(-1)
             return torch.sigmoid(y) if self.sigmoid else y
 
@@ -315,7 +263,7 @@ class mlp_score(nn.Module):  # noqa: N801  (name kept for drop-in compatibility)
         if self.training and self.dropout > 0:
             raise NotImplementedError("training-mode dropout without autograd: use model.eval() for inference")
         with torch.no_grad():
-            h = _as_f32_rows(x)
+            h = f32_rows(x)
             if len(self.lins) == 2 and self.lins[1].out_features == 1:  # Linear -> ReLU -> dot -> sigmoid, one launch
                 l1, l2 = self.lins
                 t = self._chain.tables(l1.weight, l1.bias, None, None, l2.weight, l2.bias)
@@ -323,7 +271,7 @@ class mlp_score(nn.Module):  # noqa: N801  (name kept for drop-in compatibility)
                 if res is not None:
                     return res
             for i, lin in enumerate(self.lins[:-1]):
-                h = gemm(h, self._pads[i].get(lin.weight), lin.bias, relu=True)
+                h = gemm(h, self._pads[i].get(lin.weight), lin.bias, relu=True, tag="gemm")
             return self._tail(h, want_prob)
 
     def _tail(self, h: torch.Tensor, want_prob: bool) -> torch.Tensor:
@@ -340,10 +288,10 @@ class mlp_score(nn.Module):  # noqa: N801  (name kept for drop-in compatibility)
                 b = self._bias_val
             check(_lib.hip().lpf_rowdot_sigmoid_f32(h.shape[0], h.shape[1], ptr(h), h.stride(0), ptr(w), b,
                                                     None if want_prob else ptr(res),
-                                                    ptr(res) if want_prob else None, _stream(h.device)),
+                                                    ptr(res) if want_prob else None, raw_stream(h.device)),
                   "lpf_rowdot_sigmoid_f32")
             return res
-        y = gemm(h, self._pads[-1].get(last.weight), last.bias)
+        y = gemm(h, self._pads[-1].get(last.weight), last.bias, tag="gemm")
         return torch.sigmoid(y).squeeze(-1) if want_prob else y.squeeze(-1)
 
     def forward(self, x):
@@ -787,13 +735,13 @@ class LinkTransformer(nn.Module):
         x = self.data["x"]
         hit = self._x_cache
         if hit is None or hit[0] is not x or hit[1] != x._version:  # identity, not address (see _node_keys)
-            hit = self._x_cache = (x, x._version, _as_f32_rows(x.detach().to(self.device)))
+            hit = self._x_cache = (x, x._version, f32_rows(x.detach().to(self.device)))
         return hit[2]
 
     def _workspace(self, name: str, numel: int, dtype, st=None) -> torch.Tensor:
         """Named scratch buffer of the CURRENT stream (callers may pipeline batches on several streams; each stream
         owns its own set, allocated under that stream so the caching allocator orders its reuse correctly)."""
-        key = (name, st if st is not None else _stream(self.device))
+        key = (name, st if st is not None else raw_stream(self.device))
         t = self._ws.get(key)
         if t is None or t.numel() < numel or t.dtype != dtype:
             grow = int(numel * 1.25) + 64
@@ -804,7 +752,7 @@ class LinkTransformer(nn.Module):
     def _zero_workspace(self, name: str, numel: int, st=None) -> torch.Tensor:
         """``_workspace`` whose memory is zero when it is (re)allocated: for buffers with padding columns that the
         kernels never write and the consumers read."""
-        key = (name, st if st is not None else _stream(self.device))
+        key = (name, st if st is not None else raw_stream(self.device))
         t = self._ws.get(key)
         if t is None or t.numel() < numel:
             t = self._ws[key] = torch.zeros(int(numel * 1.25) + 64, dtype=torch.float32, device=self.device)
@@ -891,7 +839,7 @@ class LinkTransformer(nn.Module):
                     if self._fusable(i, x.shape[1]):
                         if x_full is None:
                             x_full = lpf_dist.allgather_rows(x, self.num_nodes)
-                        x = self._layer_fused(i, a_hat, _as_f32_rows(x_full), lo, hi)
+                        x = self._layer_fused(i, a_hat, f32_rows(x_full), lo, hi)
                     else:
                         t = lpf_dist.allgather_rows(self._layer_transform(i, x), self.num_nodes)   # [N, D] everywhere
                         x = self._layer_aggregate(i, a_hat, t, lo, hi, x)
@@ -904,7 +852,7 @@ class LinkTransformer(nn.Module):
     def _layer(self, i: int, a_hat: graph.DeviceCSR, x: torch.Tensor, lo: int, hi: int) -> torch.Tensor:
         """Rows [lo, hi) of layer i's output from the layer input ``x`` of ALL nodes: one launch when the layer is
         square and small enough for the fused kernel, transform + aggregate otherwise."""
-        x = _as_f32_rows(x)
+        x = f32_rows(x)
         if self._fusable(i, x.shape[1]):
             return self._layer_fused(i, a_hat, x, lo, hi)
         return self._layer_aggregate(i, a_hat, self._layer_transform(i, x), lo, hi, x[lo:hi])
@@ -925,7 +873,7 @@ class LinkTransformer(nn.Module):
         d = x.shape[1]
         last = i == len(enc.convs) - 1
         b16 = self.encoder_precision == "bf16"
-        lib, st = _lib.hip(), _stream(self.device)
+        lib, st = _lib.hip(), raw_stream(self.device)
         cache = a_hat.__dict__.setdefault("_fused_order", {})
         key = (lo, hi, b16)
         if key not in cache:
@@ -934,35 +882,29 @@ class LinkTransformer(nn.Module):
         ln = enc.lns[i] if enc.lns is not None else None
         res = x[lo:hi] if enc.residual else None
         out = torch.empty(hi - lo, d, dtype=torch.float32, device=self.device)
-        xb = self._bf16p(x) if b16 else None
+        xin = self._bf16p(x) if b16 else x      # the table the rows are gathered from
         t_parts = None
         if hubs is not None:   # hub rows: their slices are summed first, the layer kernel reads the sums
             t_parts = self._workspace("gcn_t_parts", parts.shape[0] * d, torch.float32, st)
+            name = "lpf_spmm_row_parts_bf16p" if b16 else "lpf_spmm_row_parts_f32"
             with KernelTimer.span("spmm_row_parts"):
-                if b16:
-                    check(lib.lpf_spmm_row_parts_bf16p(d, ptr(parts), parts.shape[0], ptr(a_hat.col), ptr(a_hat.val),
-                                                       ptr(xb), xb.stride(0), ptr(t_parts), st), "lpf_spmm_row_parts_bf16p")
-                else:
-                    check(lib.lpf_spmm_row_parts_f32(d, ptr(parts), parts.shape[0], ptr(a_hat.col), ptr(a_hat.val),
-                                                     ptr(x), x.stride(0), ptr(t_parts), st), "lpf_spmm_row_parts_f32")
+                check(getattr(lib, name)(d, ptr(parts), parts.shape[0], ptr(a_hat.col), ptr(a_hat.val), ptr(xin),
+                                         xin.stride(0), ptr(t_parts), st), name)
         common = (ptr(self._conv_packs[i].get(conv.lin.weight)), ptr(out), out.stride(0), ptr(conv.bias),
                   ptr(ln.weight) if ln is not None else None, ptr(ln.bias) if ln is not None else None,
                   ptr(res), 0 if res is None else res.stride(0),
                   ptr(self.gnn_norm.weight) if last else None, ptr(self.gnn_norm.bias) if last else None,
                   FLAG_RELU if enc.relu else 0, ptr(hubs), ptr(t_parts))
+        name = "lpf_gcn_layer_fused_bf16" if b16 else "lpf_gcn_layer_fused_f32"
         with KernelTimer.span("gcn_layer_fused"):
-            if b16:
-                whole = lo == 0 and hi == self.num_nodes and not last
-                out_b = torch.empty(hi - lo, d, dtype=torch.bfloat16, device=self.device) if whole else None
-                check(lib.lpf_gcn_layer_fused_bf16(
-                    d, order.numel() // 16, ptr(order), lo, ptr(a_hat.rowptr), ptr(a_hat.col), ptr(a_hat.val), ptr(xb),
-                    xb.stride(0), *common, ptr(out_b), d, st), "lpf_gcn_layer_fused_bf16")
-                if whole:
-                    self._xb_cache = (weakref.ref(out), out_b)
-            else:
-                check(lib.lpf_gcn_layer_fused_f32(
-                    d, order.numel() // 16, ptr(order), lo, ptr(a_hat.rowptr), ptr(a_hat.col), ptr(a_hat.val), ptr(x),
-                    x.stride(0), *common, None, 0, st), "lpf_gcn_layer_fused_f32")
+            # (bf16, a whole-graph layer that is not the last: the bf16 image of the output, for the next layer)
+            whole = b16 and lo == 0 and hi == self.num_nodes and not last
+            out_b = torch.empty(hi - lo, d, dtype=torch.bfloat16, device=self.device) if whole else None
+            check(getattr(lib, name)(
+                d, order.numel() // 16, ptr(order), lo, ptr(a_hat.rowptr), ptr(a_hat.col), ptr(a_hat.val), ptr(xin),
+                xin.stride(0), *common, ptr(out_b), d if b16 else 0, st), name)
+            if whole:
+                self._xb_cache = (weakref.ref(out), out_b)
         return out
 
     def _bf16p(self, x: torch.Tensor) -> torch.Tensor:
@@ -987,7 +929,7 @@ class LinkTransformer(nn.Module):
         gathers -- and, row-sharded, the tensor that crosses xGMI."""
         conv = self.node_encoder.gnn_encoder.convs[i]
         w = self._conv_pads[i].get(conv.lin.weight)
-        a = _as_f32_rows(x_rows)
+        a = f32_rows(x_rows)
         if self.encoder_precision != "bf16":
             return gemm(a, w, tag="gemm_encoder")
         m, k = a.shape
@@ -996,7 +938,7 @@ class LinkTransformer(nn.Module):
         out = torch.empty(m, ld, dtype=torch.bfloat16, device=a.device)[:, :n]
         with KernelTimer.span("gemm_encoder"):
             check(_lib.hip().lpf_gemm_f32_out_bf16(m, n, k, ptr(a), a.stride(0), ptr(w), w.stride(0), None, None, 0,
-                                                   ptr(out), out.stride(0), 0, _stream(a.device)),
+                                                   ptr(out), out.stride(0), 0, raw_stream(a.device)),
                   "lpf_gemm_f32_out_bf16")
         return out
 
@@ -1011,30 +953,8 @@ class LinkTransformer(nn.Module):
         last = i == len(enc.convs) - 1
         res = x_rows if (enc.residual and x_rows.shape[1] == d) else None
         ln = enc.lns[i] if enc.lns is not None else None
-        long_rows = self._long_rows(a_hat, lo, hi)
-        out = torch.empty(hi - lo, d, dtype=torch.float32, device=self.device)
-        bf16 = t.dtype == torch.bfloat16
-        fn = _lib.hip().lpf_spmm_csr_bf16 if bf16 else _lib.hip().lpf_spmm_csr_f32
-        with KernelTimer.span("spmm_csr"):
-            check(fn(
-                hi - lo, d, a_hat.rowptr.data_ptr() + 8 * lo, ptr(a_hat.col), ptr(a_hat.val), ptr(t),
-                t.stride(0), ptr(out), out.stride(0), ptr(conv.bias),
-                ptr(ln.weight) if ln is not None else None, ptr(ln.bias) if ln is not None else None,
-                ptr(res), 0 if res is None else res.stride(0),
-                ptr(self.gnn_norm.weight) if last else None, ptr(self.gnn_norm.bias) if last else None,
-                FLAG_RELU if enc.relu else 0, ptr(long_rows), 0 if long_rows is None else long_rows.numel(),
-                _stream(self.device)), "lpf_spmm_csr_bf16" if bf16 else "lpf_spmm_csr_f32")
-        return out
-
-    def _long_rows(self, a_hat: graph.DeviceCSR, lo: int, hi: int):
-        """Hub rows (> LPF_SPMM_LONG_ROW entries) of the local row block, as row ids relative to `lo`; cached on the
-        device graph itself, so the list lives exactly as long as the graph it describes."""
-        cache = a_hat.__dict__.setdefault("_long_rows", {})
-        if (lo, hi) not in cache:
-            deg = (a_hat.rowptr[lo + 1:hi + 1] - a_hat.rowptr[lo:hi])
-            rows = torch.nonzero(deg > 128).flatten().to(torch.int32)
-            cache[(lo, hi)] = rows if rows.numel() else None
-        return cache[(lo, hi)]
+        return ops.spmm(a_hat, t, lo, hi, bias=conv.bias, ln=ln, res=res, final_ln=self.gnn_norm if last else None,
+                        relu=enc.relu, tag="spmm_csr")
 
     def set_row_shard(self, rank: int, world: int, mode: str = "sharded"):
         """This process is rank ``rank`` of ``world`` (default process group, lpformer_amd/dist.py).  ``mode``:
@@ -1059,7 +979,7 @@ class LinkTransformer(nn.Module):
         # propagate(), so neither data_ptr nor _version alone can tell two encoder outputs apart; a tensor object can.
         hit = self._z_cache
         if hit is None or hit[0]() is not x_node or hit[1] != x_node._version:
-            xr = _as_f32_rows(x_node)
+            xr = f32_rows(x_node)
             if self.query_from == "table" and 2 * self.dim <= 256:
                 # the query table Y will be asked for next: ONE [N, D] x [D, 2D] product leaves both, Z and Y being the
                 # two halves of its rows (one launch and one pass over X; the time is the matrix pipe's either way:
@@ -1079,7 +999,7 @@ class LinkTransformer(nn.Module):
         reference's expression (layers.py:212-215) -- is a gather-add per batch instead of a product."""
         hit = getattr(self, "_y_cache", None)
         if hit is None or hit[0]() is not x_node or hit[1] != x_node._version:
-            y = gemm(_as_f32_rows(x_node), w["w_l"], w["b_l"], tag="gemm_node_query")
+            y = gemm(f32_rows(x_node), w["w_l"], w["b_l"], tag="gemm_node_query")
             torch.cuda.current_stream(self.device).synchronize()  # once per encoder output: other streams read Y
             hit = self._y_cache = (weakref.ref(x_node), x_node._version, y)
         return hit[2]
@@ -1093,21 +1013,15 @@ class LinkTransformer(nn.Module):
         ``test_edge`` pattern, one encoder pass per batch)."""
         if self.query_from == "table":
             y = self._node_y(x_node, w)
-            bs, d = batch.shape[1], self.dim
-            q = torch.empty(bs, d, dtype=torch.float32, device=self.device)
-            with KernelTimer.span("pair_gather_q"):
-                check(_lib.hip().lpf_pair_gather_f32(bs, d, ptr(batch), batch.stride(0), y.shape[0], ptr(y), y.stride(0),
-                                                     None, 0, ptr(q), d, _stream(self.device)), "lpf_pair_gather_f32")
+            q = torch.empty(batch.shape[1], self.dim, dtype=torch.float32, device=self.device)
+            ops.pair_gather(y, batch, sum=q, tag="pair_gather_q")
             return q
         lin_l = self.att_layers[0].att.lin_l
         t = self._chain_q.tables(lin_l.weight, w["b_l2"])
         q = self._chain_q.run(t, x_node, relu=False, batch=batch, in_mode=2)
         if q is None:   # (a shape without a fused instantiation: gather-add, then the plain product)
-            bs, d = batch.shape[1], x_node.shape[1]
-            xs = torch.empty(bs, d, dtype=torch.float32, device=self.device)
-            check(_lib.hip().lpf_pair_gather_f32(bs, d, ptr(batch), batch.stride(0), x_node.shape[0], ptr(x_node),
-                                                 x_node.stride(0), None, 0, ptr(xs), d, _stream(self.device)),
-                  "lpf_pair_gather_f32")
+            xs = torch.empty(batch.shape[1], x_node.shape[1], dtype=torch.float32, device=self.device)
+            ops.pair_gather(x_node, batch, sum=xs)
             q = gemm(xs, lin_l.weight, w["b_l2"], tag="pair_q")
         return q
 
@@ -1136,7 +1050,7 @@ class LinkTransformer(nn.Module):
         with KernelTimer.span("select_regions"):
             check(_lib.hip().lpf_select4_regions(batch.shape[1], ptr(ws.pair_tab), ptr(ws.blk_types), ptr(ws.entries4),
                                                  ws.ent_cap4, ptr(ws.type_ptr), ptr(ws.entries), ws.ent_cap, ptr(ws.ctl),
-                                                 _stream(self.device)), "lpf_select4_regions")
+                                                 raw_stream(self.device)), "lpf_select4_regions")
 
     def _uses_select4_regions(self, adj_mask=None) -> bool:
         """True when the type-major consumers sit behind lpf_select4 + lpf_select4_regions."""
@@ -1147,7 +1061,7 @@ class LinkTransformer(nn.Module):
         (a block reserves its candidate slots in the pair-major buffer, the regions hold the kept entries), a batch that
         does not fit raises the sticky bits (NaN scores, ``check_selection()`` sizes again), the first batch of a
         (stream, batch size) is sized exactly with synchronisations."""
-        st = _stream(self.device)
+        st = raw_stream(self.device)
         bs = batch.shape[1]
         ws = self._sel_ws(st, bs, regions=True)
         wi = self._select_graphs(test_set, None)
@@ -1174,7 +1088,7 @@ class LinkTransformer(nn.Module):
         """The two selection launches on the current stream; no host sync.  ``graphs`` is a ``graph.WalkIndex`` (the
         evaluation path, lpf_select3_*) or the tuple of the general path (adjacency override: lpf_select_plan / _run
         over the raw PPR rows)."""
-        lib, st = _lib.hip(), _stream(self.device)
+        lib, st = _lib.hip(), raw_stream(self.device)
         bs = batch.shape[1]
         if isinstance(graphs, graph.WalkIndex):
             wi, cn = graphs, 1 if self.mask == "cn" else 0
@@ -1253,7 +1167,7 @@ class LinkTransformer(nn.Module):
         workspace.  The first batch of a (stream, batch size) is sized exactly, with one synchronisation."""
         if self._uses_select4_regions(adj_mask):
             return self._select_regions_device(batch, test_set)
-        st = _stream(self.device)
+        st = raw_stream(self.device)
         bs = batch.shape[1]
         ws = self._sel_ws(st, bs, regions=False)
         graphs = self._select_graphs(test_set, adj_mask)
@@ -1328,7 +1242,7 @@ class LinkTransformer(nn.Module):
     def _select4_launch(self, ws, batch, wi, regions: bool = False):
         """``lpf_select4`` into ``ws`` (a ``_Select4Workspace``, or -- ``regions`` -- the pair-major half of a
         ``_Select4RegionsWorkspace``)."""
-        lib, st = _lib.hip(), _stream(self.device)
+        lib, st = _lib.hip(), raw_stream(self.device)
         cn = 1 if self.mask == "cn" else 0
         with KernelTimer.span("select_run"):
             check(lib.lpf_select4(batch.shape[1], ptr(batch), batch.stride(0), self.num_nodes, ptr(wi.rec), ptr(wi.adj_cv),
@@ -1345,7 +1259,7 @@ class LinkTransformer(nn.Module):
         slots, which the kernel reports in ``ctl[0]``); a batch that does not fit raises the sticky error bits, its
         scores come out as NaN and ``check_selection()`` sizes the buffer again.  The first batch of a (stream, batch
         size) is sized exactly, with one synchronisation."""
-        st = _stream(self.device)
+        st = raw_stream(self.device)
         bs = batch.shape[1]
         key = ("sel4", st, bs)
         ws = self._ws.get(key)
@@ -1437,9 +1351,8 @@ class LinkTransformer(nn.Module):
         g = graph.gcn_norm_device(graph.DeviceCSR(own.rowptr, own.col, new_w, own.n, None))
         for k in ("_fused_order", "_long_rows"):      # (functions of the structure alone: one dict for both graphs)
             g.__dict__[k] = own.__dict__.setdefault(k, {})
-        for k in ("_long_rows_full", "_edge_keys"):
-            if k in own.__dict__:
-                g.__dict__[k] = own.__dict__[k]
+        if "_edge_keys" in own.__dict__:
+            g.__dict__["_edge_keys"] = own.__dict__["_edge_keys"]
         g.__dict__["_structure_of"] = own
         return g
 
@@ -1485,7 +1398,7 @@ class LinkTransformer(nn.Module):
             out = torch.empty(rows.numel(), dtype=torch.float32, device=self.device)
             rows, cols = rows.contiguous(), cols.contiguous()
             check(_lib.hip().lpf_csr_lookup_f32(rows.numel(), ppr.n, ptr(rows), ptr(cols), ptr(ppr.rowptr), ptr(ppr.col),
-                                                ptr(ppr.val), ptr(out), _stream(self.device)), "lpf_csr_lookup_f32")
+                                                ptr(ppr.val), ptr(out), raw_stream(self.device)), "lpf_csr_lookup_f32")
             return out
         return lookup
 
@@ -1516,9 +1429,9 @@ class LinkTransformer(nn.Module):
             rk = self._mask_delta(adj_mask, test_set)
             if rk is not None:
                 return self._select_patched(batch, test_set, rk)
-        lib, st = _lib.hip(), _stream(self.device)
+        lib, st = _lib.hip(), raw_stream(self.device)
         bs = batch.shape[1]
-        ldf = _pad4(self.dim + self.count_dim)
+        ldf = pad4(self.dim + self.count_dim)
         feats = torch.empty(bs, ldf, dtype=torch.float32, device=self.device)  # [att out | counts | pad]
         if ldf > self.dim + self.count_dim:
             feats[:, self.dim + self.count_dim:].zero_()  # the attention output and the counts are written below
@@ -1788,7 +1701,7 @@ class LinkTransformer(nn.Module):
         n_counts count features]`` (``out``: [BS, ld] fp32, ld % 4 == 0).  Returns the selection workspace; with
         ``order`` also (perm int32[BS], n_nonempty int64[1]): the pairs with selected nodes first, for
         ``lpf_tail_chain_rows_perm_*``."""
-        lib, st, d = _lib.hip(), _stream(self.device), self.dim
+        lib, st, d = _lib.hip(), raw_stream(self.device), self.dim
         bs = batch.shape[1]
         w = self._fold()
         z = self._node_keys(x_node, w)
@@ -1833,7 +1746,7 @@ class LinkTransformer(nn.Module):
         """q gather (side stream) -> selection (two launches, nothing read back) -> one-pass attention.  Returns the
         selection workspace and the record buffers (part, bnd, units_cap) for ``lpf_tail_chain_merge_*`` /
         ``lpf_pair_attention_merge_f32``."""
-        lib, st, d = _lib.hip(), _stream(self.device), self.dim
+        lib, st, d = _lib.hip(), raw_stream(self.device), self.dim
         bs = batch.shape[1]
         w = self._fold()
         z = self._node_keys(x_node, w)
@@ -1847,31 +1760,21 @@ class LinkTransformer(nn.Module):
         units_cap = (ws.ent_cap + 15) // 16 + 1
         part = self._workspace("att_part", 3 * bs * rs, torch.float32, st)
         bnd = self._workspace("att_bnd", 3 * units_cap * 2 * rs, torch.float32, st)
+        b16 = self.precision == "bf16"
         with KernelTimer.span("pair_attention_fused"):
-            if self.precision == "bf16" and self.attention_kernel() == "flip":
-                zb = self._z_bf16(z)      # bf16 node table, fp32 arithmetic (no D x D product to run in bf16)
-                check(lib.lpf_pair_attention_flip_zbf16(
-                    d, bs, ptr(ws.type_ptr), ptr(ws.entries), ws.ent_cap, ptr(zb), zb.stride(0), ptr(q), q.stride(0),
+            zt = self._z_bf16(z) if b16 else z      # bf16 node table, fp32 arithmetic (no D x D product to run in bf16)
+            if self.attention_kernel() == "flip":
+                name = "lpf_pair_attention_flip" + ("_zbf16" if b16 else "_f32")
+                check(getattr(lib, name)(
+                    d, bs, ptr(ws.type_ptr), ptr(ws.entries), ws.ent_cap, ptr(zt), zt.stride(0), ptr(q), q.stride(0),
                     ptr(w["flip_tab"]), ptr(w["pe_stat"]), ptr(w["flip_base"]), ptr(w["wfold_t"]),
-                    ptr(w["att"]), ptr(part), ptr(bnd), units_cap, st), "lpf_pair_attention_flip_zbf16")
-            elif self.precision == "bf16":
-                zb = self._z_bf16(z)
-                check(lib.lpf_pair_attention_fused_bf16(
-                    d, bs, ptr(ws.type_ptr), ptr(ws.entries), ws.ent_cap, ptr(zb), zb.stride(0), ptr(q),
-                    q.stride(0), ptr(w["pe_tab"]), ptr(w["pe_stat"]), ptr(w["wfold_packed_bf16"]),
-                    ptr(w["bfold"]), ptr(w["att"]), ptr(part), ptr(bnd), units_cap, st),
-                    "lpf_pair_attention_fused_bf16")
-            elif self.attention_kernel() == "flip":
-                check(lib.lpf_pair_attention_flip_f32(
-                    d, bs, ptr(ws.type_ptr), ptr(ws.entries), ws.ent_cap, ptr(z), z.stride(0), ptr(q), q.stride(0),
-                    ptr(w["flip_tab"]), ptr(w["pe_stat"]), ptr(w["flip_base"]), ptr(w["wfold_t"]),
-                    ptr(w["att"]), ptr(part), ptr(bnd), units_cap, st), "lpf_pair_attention_flip_f32")
+                    ptr(w["att"]), ptr(part), ptr(bnd), units_cap, st), name)
             else:
-                check(lib.lpf_pair_attention_fused_f32(
-                    d, bs, ptr(ws.type_ptr), ptr(ws.entries), ws.ent_cap, ptr(z), z.stride(0), ptr(q),
-                    q.stride(0), ptr(w["pe_tab"]), ptr(w["pe_stat"]), ptr(w["wfold_packed"]),
-                    ptr(w["bfold"]), ptr(w["att"]), ptr(part), ptr(bnd), units_cap, st),
-                    "lpf_pair_attention_fused_f32")
+                name = "lpf_pair_attention_fused" + ("_bf16" if b16 else "_f32")
+                check(getattr(lib, name)(
+                    d, bs, ptr(ws.type_ptr), ptr(ws.entries), ws.ent_cap, ptr(zt), zt.stride(0), ptr(q),
+                    q.stride(0), ptr(w["pe_tab"]), ptr(w["pe_stat"]), ptr(w["wfold_packed_bf16" if b16 else "wfold_packed"]),
+                    ptr(w["bfold"]), ptr(w["att"]), ptr(part), ptr(bnd), units_cap, st), name)
         return ws, part, bnd, units_cap
 
     def _pair_scores(self, batch, x_node, test_set, adj_mask):
@@ -1879,7 +1782,7 @@ class LinkTransformer(nn.Module):
         the selection in the reference layout (``_select``: reads its status back) and ``lpf_pair_scores_f32``.  Returns
         (selection dict, score [>= cap] -- a workspace of the current stream --, z, folded tables).  Call under
         ``torch.no_grad()`` with the model's device current."""
-        lib, st, d = _lib.hip(), _stream(self.device), self.dim
+        lib, st, d = _lib.hip(), raw_stream(self.device), self.dim
         bs = batch.shape[1]
         w = self._fold()
         z = self._node_keys(x_node, w)
@@ -1906,14 +1809,14 @@ class LinkTransformer(nn.Module):
         ``stop_after_gather``: return (G [BS, 4D+4], feats, False) right after the softmax-gather instead (the
         attention output projection then belongs to ``lpf_tail_chain_f32``)."""
         with torch.no_grad():
-            lib, st, d = _lib.hip(), _stream(self.device), self.dim
+            lib, st, d = _lib.hip(), raw_stream(self.device), self.dim
             bs = batch.shape[1]
             if (d in (32, 64, 128, 256) and self.use_fused_attention and not return_weights and not stop_after_gather
                     and bs > 0):
                 # one-pass attention on the selection regions, then the records merged straight into the feature
                 # rows [post_att_norm(attention output) | counts] -- no reference-layout export, nothing read back
                 # (a batch that overflows the selection workspace comes back as NaN: check_selection())
-                ld = (d + self.count_dim + 3) // 4 * 4
+                ld = pad4(d + self.count_dim)
                 feats = torch.empty(bs, ld, dtype=torch.float32, device=self.device)
                 if ld > d + self.count_dim:
                     feats[:, d + self.count_dim:].zero_()
@@ -1951,7 +1854,7 @@ class LinkTransformer(nn.Module):
             t = self._chain_att.tables(w["wcat"], None, layer.post_att_norm.weight, layer.post_att_norm.bias)
             if self._chain_att.run(t, g[:, d:], relu=False, addend=g[:, :d], out=att_view) is None:
                 gemm(g[:, d:], w["wcat"], None, addend=g[:, :d], out=att_view, tag="gemm_attn_out")
-                layernorm_(att_view, layer.post_att_norm.weight, layer.post_att_norm.bias)
+                layernorm_(att_view, layer.post_att_norm.weight, layer.post_att_norm.bias, tag="layernorm")
             self._last_att = att_view
             att_weights = None
             if return_weights:
@@ -1974,7 +1877,7 @@ class LinkTransformer(nn.Module):
         with torch.no_grad():
             batch = self._prep_batch(batch)
             for _attempt in range(3):
-                feats, att_weights, unchecked = self._pair_attention(batch, _as_f32_rows(X_node), test_set, adj_mask,
+                feats, att_weights, unchecked = self._pair_attention(batch, f32_rows(X_node), test_set, adj_mask,
                                                                      return_weights)
                 out = self.pairwise_lin.run(feats[:, :self.dim + self.count_dim], out=_out)
                 # The callers of this API are the reference's loops: they fetch the predictions of every batch right
@@ -2004,7 +1907,7 @@ class LinkTransformer(nn.Module):
         if hit is not None and hit[0] == key:
             return hit[1]
         we1, be1, wp1, bp1, ws0, bs0 = (p.detach().double().cpu() for p in ps)
-        kpad = _pad4(d + pd)
+        kpad = pad4(d + pd)
         a = torch.zeros(ws0.shape[0], kpad, dtype=torch.float64)
         a[:, :d] = ws0[:, :d] @ we1
         a[:, d:d + pd] = ws0[:, d:] @ wp1
@@ -2061,7 +1964,7 @@ class LinkTransformer(nn.Module):
             d, pd = self.dim, self.dim + self.count_dim
             batch = self._prep_batch(batch)
             bs = batch.shape[1]
-            x_node = _as_f32_rows(X_node)
+            x_node = f32_rows(X_node)
             a, c, kpad = self._score_fold(score_func)
             r = torch.empty(bs, kpad, dtype=torch.float32, device=self.device)  # [r_e | r_p | pad]
             ew, pw = self.elementwise_lin, self.pairwise_lin
@@ -2079,19 +1982,16 @@ class LinkTransformer(nn.Module):
                 if ew._chain1.run(t, x_node, relu=True, batch=batch, in_mode=1, out=r[:, :d], side=q_side) is None:
                     q_side = None
                     prod = torch.empty(bs, d, dtype=torch.float32, device=self.device)
-                    with KernelTimer.span("pair_gather"):
-                        check(_lib.hip().lpf_pair_gather_f32(bs, d, ptr(batch), batch.stride(0), x_node.shape[0], ptr(x_node),
-                                                             x_node.stride(0), ptr(prod), d, None, 0,
-                                                             _stream(self.device)), "lpf_pair_gather_f32")
-                    gemm(prod, ew._pads[0].get(ew.linears[0].weight), ew.linears[0].bias, out=r[:, :d])
-                    layernorm_(r[:, :d], ew.norm.weight, ew.norm.bias, relu=True)
+                    ops.pair_gather(x_node, batch, product=prod, tag="pair_gather")
+                    gemm(prod, ew._pads[0].get(ew.linears[0].weight), ew.linears[0].bias, out=r[:, :d], tag="gemm")
+                    layernorm_(r[:, :d], ew.norm.weight, ew.norm.bias, relu=True, tag="layernorm")
             if (d in (32, 64, 128, 256) and self.use_tail_chain and self.use_fused_attention and bs > 0 and
                     (self._uses_rows() or d == 256)):
                 # hot path: 2 selection launches (nothing read back) -> attention leaving finished rows -> the dense
                 # tail that is left: pairwise_lin's first layer, folded score head, sigmoid.  The rows come from the
                 # pair-major kernel or (D = 256 without it: the record-merging tail has no instantiation that wide) from
                 # the unit-major kernel + lpf_pair_attention_merge_f32
-                lib, st = _lib.hip(), _stream(self.device)
+                lib, st = _lib.hip(), raw_stream(self.device)
                 order = None
                 if self._uses_rows():
                     rows = self._zero_workspace("att_rows", bs * (d + 4), st).view(bs, d + 4)   # (pad columns stay zero)
@@ -2122,22 +2022,22 @@ class LinkTransformer(nn.Module):
                 return res
             if d in (32, 64, 128) and self.use_tail_chain and self.use_fused_attention and bs > 0:
                 # 2 selection launches (nothing read back) -> one-pass attention (records) -> merged dense tail
-                lib, st = _lib.hip(), _stream(self.device)
+                lib, st = _lib.hip(), raw_stream(self.device)
                 ws, part, bnd, units_cap = self._fused_attention(batch, x_node, test_set, adj_mask, side,
                                                                  q=q_side and q_side[1])
                 tt = self._tail_tables(score_func, a, c)
                 res = torch.empty(bs, dtype=torch.float32, device=self.device)
                 with KernelTimer.span("tail_chain"):
                     b16 = self.tail_precision == "bf16"
-                    fn = lib.lpf_tail_chain_merge_bf16 if b16 else lib.lpf_tail_chain_merge_f32
-                    check(fn(
+                    name = "lpf_tail_chain_merge_bf16" if b16 else "lpf_tail_chain_merge_f32"
+                    check(getattr(lib, name)(
                         bs, d, self.count_dim, ptr(part), ptr(bnd), units_cap, ptr(ws.type_ptr),
                         ptr(self.att_layers[0].att.bias),
                         ptr(tt["lnA_g"]), ptr(tt["lnA_b"]), ptr(tt["wB_bf16" if b16 else "wB"]), ptr(tt["bB"]),
                         ptr(tt["lnB_g"]), ptr(tt["lnB_b"]), ptr(r), r.stride(0), ptr(tt["wC_bf16" if b16 else "wC"]),
                         ptr(tt["bC"]), ptr(tt["w_dot"]),
                         ptr(tt["b_dot"]), ptr(ws.ctl), ptr(res) if logits else None, None if logits else ptr(res),
-                        st), "lpf_tail_chain_merge")
+                        st), name)
                 return res
             if d in (32, 64, 128) and self.use_tail_chain:  # attention output + pairwise hidden + head: one launch
                 g, feats, _ = self._pair_attention(batch, x_node, test_set, adj_mask, False, stop_after_gather=True)
@@ -2149,7 +2049,7 @@ class LinkTransformer(nn.Module):
                         feats.data_ptr() + 4 * d, feats.stride(0), ptr(tt["wB"]), ptr(tt["bB"]), ptr(tt["lnB_g"]),
                         ptr(tt["lnB_b"]), ptr(r), r.stride(0), ptr(tt["wC"]), ptr(tt["bC"]), ptr(tt["w_dot"]),
                         ptr(tt["b_dot"]), ptr(res) if logits else None, None if logits else ptr(res),
-                        _stream(self.device)), "lpf_tail_chain_f32")
+                        raw_stream(self.device)), "lpf_tail_chain_f32")
                 return res
             feats, _, _ = self._pair_attention(batch, x_node, test_set, adj_mask, False)  # joins the side stream
             if kpad > d + pd:
@@ -2157,13 +2057,14 @@ class LinkTransformer(nn.Module):
             xin = feats[:, :pd]
             t = pw._chain1.tables(pw.linears[0].weight, pw.linears[0].bias, pw.norm.weight, pw.norm.bias)
             if pw._chain1.run(t, xin, relu=True, out=r[:, d:d + pd]) is None:
-                gemm(xin, pw._pads[0].get(pw.linears[0].weight), pw.linears[0].bias, out=r[:, d:d + pd])
-                layernorm_(r[:, d:d + pd], pw.norm.weight, pw.norm.bias, relu=True)
+                gemm(xin, pw._pads[0].get(pw.linears[0].weight), pw.linears[0].bias, out=r[:, d:d + pd],
+                     tag="gemm")
+                layernorm_(r[:, d:d + pd], pw.norm.weight, pw.norm.bias, relu=True, tag="layernorm")
             l2 = score_func.lins[1]
             t = score_func._chain_fold.tables(a, c, None, None, l2.weight, l2.bias)
             res = score_func._chain_fold.run(t, r, relu=True, want_logit=logits)
             if res is None:
-                hid = gemm(r, a, c, relu=True)
+                hid = gemm(r, a, c, relu=True, tag="gemm")
                 res = score_func._tail(hid, not logits)
             return res
 
@@ -2195,7 +2096,7 @@ class LinkTransformer(nn.Module):
                                       "available for num_heads = 1")
         from . import train as lpf_train
         with torch.no_grad():
-            return lpf_train.pair_stage(self, _as_f32_rows(X_node), self._prep_batch(batch), adj_mask, test_set,
+            return lpf_train.pair_stage(self, f32_rows(X_node), self._prep_batch(batch), adj_mask, test_set,
                                         training=False)
 
     def _propagate_reusing(self, adj_prop, test_set):
@@ -2232,7 +2133,7 @@ class LinkTransformer(nn.Module):
             d = self.dim
             batch = self._prep_batch(batch)
             bs = batch.shape[1]
-            x_node = _as_f32_rows(X_node)
+            x_node = f32_rows(X_node)
             comb = torch.empty(bs, 2 * d, dtype=torch.float32, device=self.device)
             side = self._fork()
             with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(self.device)):

@@ -39,7 +39,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import _lib, graph, sources
+from . import _lib, graph, ops, sources
 from ._lib import check as _check_rc, ptr
 
 MAX_K = _lib.CONST["LPF_NEGATIVE_MAX_K"]
@@ -379,7 +379,7 @@ def negative_rows(source, nodes, k, *, seed, test_set: bool = False, exclude=Non
             out = torch.empty((R, k), dtype=torch.int64, device=dev)
             short = torch.zeros(1, dtype=torch.int64, device=dev)
             _check_rc(_lib.hip().lpf_negative_rows(R, known.n, ptr(ids), k, ptr(known.rowptr), ptr(known.col), seed,
-                                                   int(row_base), md, ptr(out), ptr(short), sources.raw_stream(dev)),
+                                                   int(row_base), md, ptr(out), ptr(short), ops.raw_stream(dev)),
                       "lpf_negative_rows")
     if check:
         _raise_short(int(short), R, "rows", "negative_rows")
@@ -423,7 +423,7 @@ def negative_pairs(source, num, *, seed, test_set: bool = False, exclude=None, u
             out = torch.full((2, num), -1, dtype=torch.int64, device=dev)
             nxt = torch.zeros(max(num, 1), dtype=torch.int32, device=dev)
             short = torch.zeros(1, dtype=torch.int64, device=dev)
-            hip, st = _lib.hip(), sources.raw_stream(dev)
+            hip, st = _lib.hip(), ops.raw_stream(dev)
 
             def launch(active):
                 _check_rc(hip.lpf_negative_pairs(num, n, ptr(known.rowptr), ptr(known.col), seed, int(slot_base), md,

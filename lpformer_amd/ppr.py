@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .ops import raw_stream
 from .graph import CSR, csr_from_coo
 
 
@@ -70,7 +71,7 @@ def calc_ppr_gpu(edge_index, num_nodes: int, alpha: float = 0.15, eps: float = 5
     t = mark("host_csr_s", t)
     n = int(num_nodes)
     lib = _lib.hip()
-    st = torch.cuda.current_stream(dev).cuda_stream
+    st = raw_stream(dev)
     rowptr = torch.from_numpy(np.ascontiguousarray(g.rowptr, dtype=np.int64)).to(dev)
     col = torch.from_numpy(np.ascontiguousarray(g.col, dtype=np.int32)).to(dev)
     if n == 0:

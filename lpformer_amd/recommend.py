@@ -24,7 +24,8 @@ import torch
 
 from . import _lib, graph
 from ._lib import check, ptr
-from .sources import model_graphs, node_ids, raw_stream
+from .ops import raw_stream
+from .sources import model_graphs, node_ids
 
 MAX_K = _lib.CONST["LPF_TOPK_MAX_K"]
 CANDIDATE_MODES = ("ppr", "all", "2hop")

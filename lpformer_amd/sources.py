@@ -1,9 +1,8 @@
-"""The front end the pair-analysis entry points share: where a call gets its pairs, its graphs, its
-stream and its chunks from.  Nothing here belongs to one feature.
+"""The front end the pair-analysis entry points share: where a call gets its pairs, its graphs and
+its chunks from.  Nothing here belongs to one feature.
 
     as_pairs / node_ids         edges -> [2, P] / 1-D integer ids, the caller's exception type on a wrong dtype
     clamp_chunk / chunks        pairs per launch, and the (lo, m) of each launch
-    raw_stream                  the current raw HIP stream of a device
     per_object / uploaded       per-object state kept while the object lives; the cached upload of a host CSR
     model_graphs / resolve      source -> (device, adjacency, PPR matrix, node features)
     csr_rows                    the entries of some rows of a host CSR, for the numpy restatements
@@ -53,11 +52,6 @@ def chunks(P: int, chunk: int):
     """(lo, m) of each launch over ``P`` pairs, ``chunk`` at a time."""
     for lo in range(0, P, chunk):
         yield lo, min(chunk, P - lo)
-
-
-def raw_stream(dev) -> int:
-    """The current raw HIP stream of ``dev`` (a ``torch.device``; no index: the current device)."""
-    return torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
 
 
 # ----------------------------------------------------------------------------------------------------------- caches

@@ -32,7 +32,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _lib, graph, sources
+from . import _lib, graph, ops, sources
 from ._lib import check, ptr
 
 MAX_T = _lib.CONST["LPF_THRESH_MAX_T"]
@@ -262,7 +262,7 @@ def threshold_profile(source, edges, thresholds=DEFAULT_GRID, *, test_set: bool 
         ne = torch.zeros(3, T, dtype=torch.int64, device=dev)
         pp = torch.empty(P, 3, T, dtype=torch.int32, device=dev) if per_pair else None
         if P:
-            st = sources.raw_stream(dev)
+            st = ops.raw_stream(dev)
             scratch = torch.empty(min(P, chunk) + 1, dtype=torch.int32, device=dev)
             for lo, m in sources.chunks(P, chunk):
                 check(_lib.hip().lpf_threshold_profile(

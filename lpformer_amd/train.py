@@ -30,44 +30,9 @@ import weakref
 import torch
 import torch.nn.functional as F
 
-from . import _lib, graph
+from . import _lib, graph, ops
 from ._lib import check, ptr
-
-
-def _stream(t: torch.Tensor):
-    return torch._C._cuda_getCurrentRawStream(t.device.index if t.device.index is not None
-                                              else torch.cuda.current_device())
-
-
-def _rows4(x: torch.Tensor) -> torch.Tensor:
-    """fp32, 2-D, inner stride 1, row stride a multiple of 4 floats and 16-byte aligned (what lpf_gemm_f32 wants);
-    zero-padded copy when needed."""
-    x = x.detach()
-    if x.dtype != torch.float32:
-        x = x.float()
-    if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16 or x.stride(0) < x.shape[1]:
-        k = x.shape[1]
-        buf = torch.zeros(x.shape[0], (k + 3) & ~3, dtype=torch.float32, device=x.device)
-        buf[:, :k] = x
-        x = buf[:, :k]
-    return x
-
-
-def _gemm(a: torch.Tensor, w: torch.Tensor, bias=None) -> torch.Tensor:
-    """a [M, K] @ w[N, K]^T (+ bias) -> [M, N] through lpf_gemm_f32 (the bias rides in the kernel's epilogue)."""
-    a, w = _rows4(a), _rows4(w)
-    m, k = a.shape
-    n = w.shape[0]
-    out = torch.empty(m, (n + 3) & ~3, dtype=torch.float32, device=a.device)[:, :n]
-    if m == 0 or n == 0:
-        return out
-    if k == 0:
-        return out.zero_() if bias is None else out.copy_(bias.detach().expand(m, n))
-    if bias is not None:
-        bias = bias.detach().float().contiguous()
-    check(_lib.hip().lpf_gemm_f32(m, n, k, ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), None, 0, ptr(out),
-                                  out.stride(0), 0, _stream(a)), "lpf_gemm_f32")
-    return out
+from .ops import f32_rows, gemm, raw_stream
 
 
 def _gemm_tn(a: torch.Tensor, b: torch.Tensor, colsum: bool = False):
@@ -82,10 +47,10 @@ def _gemm_tn(a: torch.Tensor, b: torch.Tensor, colsum: bool = False):
     if colsum and n > 0 and k > 0:
         cs = torch.empty(n, dtype=torch.float32, device=a.device)
         check(lib.lpf_gemm_tn_colsum_f32(m, n, k, ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), out.stride(0),
-                                         ptr(cs), ptr(ws), _stream(a)), "lpf_gemm_tn_colsum_f32")
+                                         ptr(cs), ptr(ws), raw_stream(a.device)), "lpf_gemm_tn_colsum_f32")
         return out, cs
     check(lib.lpf_gemm_tn_f32(m, n, k, ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), out.stride(0), ptr(ws),
-                              _stream(a)), "lpf_gemm_tn_f32")
+                              raw_stream(a.device)), "lpf_gemm_tn_f32")
     return (out, _colsum(a)) if colsum else out
 
 
@@ -97,7 +62,7 @@ def _colsum(x: torch.Tensor) -> torch.Tensor:
     out = torch.empty(d, dtype=torch.float32, device=x.device)
     lib = _lib.hip()
     ws = torch.empty(int(lib.lpf_train_partial_blocks(m)) * d, dtype=torch.float32, device=x.device)
-    check(lib.lpf_colsum_f32(m, d, ptr(x), x.stride(0), ptr(out), ptr(ws), _stream(x)), "lpf_colsum_f32")
+    check(lib.lpf_colsum_f32(m, d, ptr(x), x.stride(0), ptr(out), ptr(ws), raw_stream(x.device)), "lpf_colsum_f32")
     return out
 
 
@@ -131,7 +96,7 @@ class LinearFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
-        return _gemm(x, weight, bias)      # a fresh tensor: nothing else holds it
+        return gemm(x, weight, bias)      # a fresh tensor: nothing else holds it
 
     @staticmethod
     def backward(ctx, dy):
@@ -139,7 +104,7 @@ class LinearFn(torch.autograd.Function):
         dy = dy.contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = _gemm(dy, _transposed(weight)).contiguous()            # [M, N] @ [K, N]^T
+            dx = gemm(dy, _transposed(weight)).contiguous()            # [M, N] @ [K, N]^T
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1] and want_db:
             dw, db = _gemm_tn(dy, x, colsum=True)                         # dY^T X and dY^T 1 in one pass over dY
@@ -156,19 +121,7 @@ def linear(x, weight, bias=None):
 
 def _spmm_plain(a: graph.DeviceCSR, h: torch.Tensor, bias=None) -> torch.Tensor:
     """out = A h (+ bias) through lpf_spmm_csr_f32 (no other epilogue)."""
-    h = _rows4(h)
-    n, d = a.n, h.shape[1]
-    out = torch.empty(n, d, dtype=torch.float32, device=h.device)
-    deg = a.rowptr[1:] - a.rowptr[:-1]
-    cache = a.__dict__.setdefault("_long_rows_full", None)
-    if cache is None:
-        rows = torch.nonzero(deg > 128).flatten().to(torch.int32)
-        cache = a.__dict__["_long_rows_full"] = (rows if rows.numel() else False)
-    long_rows = cache if cache is not False else None
-    check(_lib.hip().lpf_spmm_csr_f32(n, d, ptr(a.rowptr), ptr(a.col), ptr(a.val), ptr(h), h.stride(0), ptr(out),
-                                      out.stride(0), ptr(bias), None, None, None, 0, None, None, 0, ptr(long_rows),
-                                      0 if long_rows is None else long_rows.numel(), _stream(h)), "lpf_spmm_csr_f32")
-    return out
+    return ops.spmm(a, f32_rows(h), bias=bias)
 
 
 def _transpose_csr(a: graph.DeviceCSR) -> graph.DeviceCSR:
@@ -184,12 +137,8 @@ def _transpose_csr(a: graph.DeviceCSR) -> graph.DeviceCSR:
         # functions of the structure alone -- the one-launch layer's degree-ordered tiles and hub slices, the long-row
         # list of lpf_spmm_csr_f32 -- are the resident transposed graph's (recomputing them was a sort over the rows
         # and a host synchronisation per batch: 1.7 of the 15 ms of a step that overrides the propagation matrix)
-        hit.__dict__["_fused_order"] = t.__dict__.setdefault("_fused_order", {})
-        if t.__dict__.get("_long_rows_full") is None:
-            deg = t.rowptr[1:] - t.rowptr[:-1]
-            rows = torch.nonzero(deg > 128).flatten().to(torch.int32)
-            t.__dict__["_long_rows_full"] = rows if rows.numel() else False
-        hit.__dict__["_long_rows_full"] = t.__dict__["_long_rows_full"]
+        for k in ("_fused_order", "_long_rows"):
+            hit.__dict__[k] = t.__dict__.setdefault(k, {})
     if hit is None:
         n = a.n
         rows = torch.repeat_interleave(torch.arange(n, device=a.col.device), a.rowptr[1:] - a.rowptr[:-1])
@@ -224,8 +173,7 @@ class LayerNormFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         y = torch.empty_like(x2)
-        check(_lib.hip().lpf_layernorm_f32(x2.shape[0], x2.shape[1], ptr(x2), x2.stride(0), ptr(weight), ptr(bias),
-                                           ptr(y), y.stride(0), 0, _stream(x2)), "lpf_layernorm_f32")
+        ops.layernorm_(x2, weight, bias, out=y)
         ctx.save_for_backward(x2, weight)
         ctx.shape = x.shape
         return y.reshape(x.shape)
@@ -240,7 +188,7 @@ class LayerNormFn(torch.autograd.Function):
         lib = _lib.hip()
         ws = torch.empty(int(lib.lpf_layernorm_bwd_workspace_floats(d)), dtype=torch.float32, device=x2.device)
         check(lib.lpf_layernorm_bwd_f32(x2.shape[0], d, ptr(x2), x2.stride(0), ptr(dy2), dy2.stride(0), ptr(weight),
-                                        ptr(dx), dx.stride(0), ptr(dg), ptr(db), ptr(ws), _stream(x2)),
+                                        ptr(dx), dx.stride(0), ptr(dg), ptr(db), ptr(ws), raw_stream(x2.device)),
               "lpf_layernorm_bwd_f32")
         return dx.reshape(ctx.shape), dg, db
 
@@ -253,8 +201,7 @@ class LnReluFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         y = torch.empty_like(x2)
-        check(_lib.hip().lpf_layernorm_f32(x2.shape[0], x2.shape[1], ptr(x2), x2.stride(0), ptr(weight), ptr(bias),
-                                           ptr(y), y.stride(0), _lib.FLAG_RELU, _stream(x2)), "lpf_layernorm_f32")
+        ops.layernorm_(x2, weight, bias, relu=True, out=y)
         ctx.save_for_backward(x2, weight, bias)
         ctx.shape = x.shape
         return y.reshape(x.shape)
@@ -279,7 +226,7 @@ def _ln_relu_bwd(x2, dy2, weight, bias, drop_p: float = 0.0, drop_seed: int = 0)
     ws = torch.empty(int(lib.lpf_layernorm_bwd_workspace_floats(d)), dtype=torch.float32, device=dev)
     check(lib.lpf_layernorm_relu_drop_bwd_f32(x2.shape[0], d, ptr(x2), x2.stride(0), ptr(dy2), dy2.stride(0), ptr(weight),
                                               ptr(bias), drop_p, drop_seed, ptr(dx), dx.stride(0), ptr(dg), ptr(db),
-                                              ptr(dxs), ptr(ws), _stream(x2)), "lpf_layernorm_relu_drop_bwd_f32")
+                                              ptr(dxs), ptr(ws), raw_stream(x2.device)), "lpf_layernorm_relu_drop_bwd_f32")
     return dx, dg, db, dxs
 
 
@@ -293,8 +240,7 @@ class GcnLayerFn(torch.autograd.Function):
     def forward(ctx, t, a_hat, conv_bias, ln_w, ln_b):
         u = _spmm_plain(a_hat, t, bias=conv_bias)
         r = torch.empty_like(u)
-        check(_lib.hip().lpf_layernorm_f32(u.shape[0], u.shape[1], ptr(u), u.stride(0), ptr(ln_w), ptr(ln_b), ptr(r),
-                                           r.stride(0), _lib.FLAG_RELU, _stream(u)), "lpf_layernorm_f32")
+        ops.layernorm_(u, ln_w, ln_b, relu=True, out=r)
         ctx.save_for_backward(u, ln_w, ln_b)
         ctx.a_hat = a_hat
         return r
@@ -313,7 +259,7 @@ def _fused_layer(a: graph.DeviceCSR, x2: torch.Tensor, wp: torch.Tensor, bias=No
     out = residual + dropout(epilogue((a x2) Wp^T)) -> (out, pre-norm rows or None, aggregated rows or None).  Hub rows go
     through their slice sums first (csrc/gcn_fused.hip)."""
     n, d = a.n, x2.shape[1]
-    lib, st = _lib.hip(), _stream(x2)
+    lib, st = _lib.hip(), raw_stream(x2.device)
     cache = a.__dict__.setdefault("_fused_order", {})
     if (0, n) not in cache:
         cache[(0, n)] = graph.fused_row_order(a.rowptr, 0, n)
@@ -390,7 +336,7 @@ class GcnFusedFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, i, x, weight, a_hat, conv_bias, ln_w, ln_b, drop_p=0.0, skip=False):
-        x2 = _rows4(x)
+        x2 = f32_rows(x)
         seed = _next_drop_seed(x2.device) if drop_p > 0 else 0
         y, u, h = _fused_layer(a_hat, x2, model._conv_packs[i].get(weight), conv_bias, ln_w, ln_b, _lib.FLAG_RELU,
                                pre=True, agg=True, residual=x2 if skip else None, drop_p=drop_p, drop_seed=seed)
@@ -401,7 +347,7 @@ class GcnFusedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         h, weight, u, ln_w, ln_b = ctx.saved_tensors
-        dy = _rows4(dy)
+        dy = f32_rows(dy)
         du, dg, db, dbias = _ln_relu_bwd(u, dy, ln_w, ln_b, *ctx.drop)
         dw = _gemm_tn(du, h)
         dx = None
@@ -630,9 +576,7 @@ class PairGatherFn(torch.autograd.Function):
         x = x.contiguous()
         bs, d = batch.shape[1], x.shape[1]
         out = torch.empty(bs, d, dtype=torch.float32, device=x.device)
-        args = (ptr(out), d, None, 0) if product else (None, 0, ptr(out), d)
-        check(_lib.hip().lpf_pair_gather_f32(bs, d, ptr(batch), batch.stride(0), x.shape[0], ptr(x), x.stride(0), *args,
-                                             _stream(x)), "lpf_pair_gather_f32")
+        ops.pair_gather(x, batch, product=out if product else None, sum=None if product else out)
         ctx.save_for_backward(x, batch)
         ctx.product, ctx.end_sort = product, end_sort
         return out
@@ -650,11 +594,11 @@ class PairGatherFn(torch.autograd.Function):
             else:                 # d(x_a + x_b)
                 src = torch.cat([dout, dout])
             check(_lib.hip().lpf_segment_rows_sum_f32(2 * bs, d, ptr(keys), ptr(order), ptr(src), d, ptr(dx), dx.stride(0),
-                                                      _stream(x)), "lpf_segment_rows_sum_f32")
+                                                      raw_stream(x.device)), "lpf_segment_rows_sum_f32")
             return dx, None, None, None
         dm, ds = (dout, None) if ctx.product else (None, dout)
         check(_lib.hip().lpf_pair_scatter_add_f32(bs, d, ptr(batch), batch.stride(0), x.shape[0], ptr(x), x.stride(0),
-                                                  ptr(dm), d, ptr(ds), d, ptr(dx), dx.stride(0), _stream(x)),
+                                                  ptr(dm), d, ptr(ds), d, ptr(dx), dx.stride(0), raw_stream(x.device)),
               "lpf_pair_scatter_add_f32")
         return dx, None, None, None
 
@@ -672,7 +616,7 @@ class PairAttentionFn(torch.autograd.Function):
     def forward(ctx, z, q, att, bias, wfold, bfold, w1s, b1s, gams, bets, e_node, e_pa, e_pb, seg, tbase, node_sort=None):
         """z: rows the entries' ``e_node`` index (the node table, or -- forward_train -- its rows for the batch's distinct
         nodes); ``node_sort`` = (sorted e_node, the permutation that sorts it) when the caller has them."""
-        lib, st = _lib.hip(), _stream(z)
+        lib, st = _lib.hip(), raw_stream(z.device)
         z, q = z.contiguous(), q.contiguous()
         att, bias = att.contiguous(), bias.contiguous()
         wfold, bfold = wfold.contiguous(), bfold.contiguous()
@@ -709,7 +653,7 @@ class PairAttentionFn(torch.autograd.Function):
     def backward(ctx, dout):
         (z, q, att, bias, wfold, w1s, b1s, gams, bets, e_node, e_pa, e_pb, seg, h, kp, out, score, pmax,
          pinv) = ctx.saved_tensors
-        lib, st, tbase = _lib.hip(), _stream(z), ctx.tbase
+        lib, st, tbase = _lib.hip(), raw_stream(z.device), ctx.tbase
         dout = dout.contiguous()
         bs, d, n, dh_w = q.shape[0], q.shape[1], int(e_node.numel()), w1s.shape[1]
         dev = z.device

@@ -4,7 +4,8 @@ import pytest
 import torch
 
 from lpformer_amd import _lib, graph
-from lpformer_amd.link_transformer import DenseChain, gemm, layernorm_
+from lpformer_amd.link_transformer import DenseChain
+from lpformer_amd.ops import gemm, layernorm_
 from oracle import lpformer_oracle as O
 
 pytestmark = pytest.mark.gpu

@@ -3,7 +3,8 @@ import sys
 import torch
 
 sys.path.insert(0, ".")
-from lpformer_amd.link_transformer import DenseChain, gemm, layernorm_  # noqa: E402
+from lpformer_amd.link_transformer import DenseChain  # noqa: E402
+from lpformer_amd.ops import gemm, layernorm_  # noqa: E402
 
 DEV = "cuda:0"
 import os
