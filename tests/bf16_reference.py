@@ -96,10 +96,10 @@ def rounded(x, window, rounder=rne_bf16, carried=None):
     return rounder(x), near_midpoint(x, window), charge
 
 
-def layer_norm(x, g, b):
+def layer_norm(x, g, b, eps=LN_EPS):
     mu = x.mean(axis=-1, keepdims=True)
     xc = x - mu
-    sd = np.sqrt((xc * xc).mean(axis=-1, keepdims=True) + LN_EPS)
+    sd = np.sqrt((xc * xc).mean(axis=-1, keepdims=True) + eps)
     return xc / sd * g + b, xc / sd, sd
 
 
@@ -134,14 +134,15 @@ H_TERMS = 16   # fp32 operations behind an element of h_e: 3-term u, 6-term vari
 
 
 def attention_ref(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, round_z=False, round_h=False, round_wfold=False,
-                  drop=None, rounder=rne_bf16):
+                  drop=None, rounder=rne_bf16, ln_eps=LN_EPS, detail=False):
     """LinkAttention + post_att_norm on the folded tables:  k_e = Z[v] + Wfold_t h_e + bfold_t,  s_e = att .
     LeakyReLU_0.2(k_e * q[pair]),  PyG softmax per pair (max-shifted, + 1e-16), out = sum_e alpha_e k_e + bias -> LN.
 
     sel: per type (ix int [2, E] = (pair, node), pa, pb) or None;  z [N, D], q [bs, D] fp32;  w: ``model._fold()``
     (numpy or tensors: wfold, bfold, att, pe_tab, pe_stat).  ``drop``: (type, entry) left out (near-miss of a kernel
     that loses one entry).  Returns dict pre, post, counts [bs, 3], and the flip bound ``d_post`` of ``round_h``
-    (h_e is rounded inside the kernel) with its flag statistics."""
+    (h_e is rounded inside the kernel) with its flag statistics.  ``ln_eps``: the epsilon of post_att_norm (near-miss:
+    0).  ``detail``: also ``ent``, the per-entry quantities (pair, type, node, h, k, score, alpha) in type order."""
     z, q = _f64(z), _f64(q)
     wfold, bfold, att = _f64(w["wfold"]), _f64(w["bfold"]), _f64(w["att"])
     tab, stat = _f64(w["pe_tab"]), _f64(w["pe_stat"])
@@ -150,7 +151,7 @@ def attention_ref(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, round_z=False, roun
         z = rounder(z)
     if round_wfold:
         wfold = rounder(wfold)
-    pairs, keys, hs, charges, types = [], [], [], [], []
+    pairs, keys, hs, charges, types, nodes = [], [], [], [], [], []
     counts = np.zeros((bs, 3))
     n_flag = n_elem = 0
     for t, s in enumerate(sel):
@@ -174,8 +175,10 @@ def attention_ref(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, round_z=False, roun
         hs.append(h)
         charges.append(ch)
         types.append(np.full(pair.size, t))
+        nodes.append(node)
     pre = np.zeros((bs, d))
     d_pre = np.zeros((bs, d))
+    ent = None
     if pairs:
         pair = np.concatenate(pairs)
         k = np.concatenate(keys)
@@ -191,6 +194,9 @@ def attention_ref(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, round_z=False, roun
         np.add.at(den, pair, e)
         alpha = e / (den + 1e-16)[pair]
         np.add.at(pre, pair, k * alpha[:, None])
+        if detail:
+            ent = {"pair": pair, "type": tt, "node": np.concatenate(nodes), "h": np.concatenate(hs), "k": k,
+                   "score": score, "alpha": alpha}
         hit = np.flatnonzero(ch.any(axis=1))
         if hit.size:
             # one flipped h element moves k_e by Wfold[:, k] delta and s_e by (att q) . Wfold[:, k] delta; the output
@@ -207,9 +213,12 @@ def attention_ref(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, round_z=False, roun
             contrib = alpha[hit, None] * (dk + np.abs(k[hit] - pre[ph]) * ds[:, None])
             np.add.at(d_pre, ph, contrib)
     pre = pre + _f64(att_bias)
-    post, xhat, sd = layer_norm(pre, _f64(ln_g), _f64(ln_b))
+    post, xhat, sd = layer_norm(pre, _f64(ln_g), _f64(ln_b), ln_eps)
     d_post = ln_bound(d_pre, xhat, sd, _f64(ln_g))
-    return {"pre": pre, "post": post, "counts": counts, "d_post": d_post, "n_flag": n_flag, "n_elem": n_elem}
+    out = {"pre": pre, "post": post, "counts": counts, "d_post": d_post, "n_flag": n_flag, "n_elem": n_elem}
+    if detail:
+        out["ent"] = ent
+    return out
 
 
 def count_features(counts, n_counts):
@@ -231,14 +240,15 @@ def elementwise_hidden(x_node, batch, w0, b0, g, b):
     return np.maximum(y, 0.0)
 
 
-def tail_ref(rows, feats_cnt, r_e, t, *, round_act=False, round_w=False, lite=None, d_rows=None, rounder=rne_bf16):
+def tail_ref(rows, feats_cnt, r_e, t, *, round_act=False, round_w=False, lite=None, d_rows=None, rounder=rne_bf16,
+             ln_eps=LN_EPS):
     """pairwise_lin's first layer + LN + ReLU, then the folded score head (``LinkTransformer._score_fold``):
         r_p = ReLU(LN_B(W_p0 [row | counts] + b_p0)),  logit = w_dot . ReLU(A [r_e | r_p] + c) + b_dot.
     t: dict w_p0 [pd, pd], b_p0, lnB_g, lnB_b, A [2D, D + pd], c [2D], w_dot [2D], b_dot, and bC_empty (lite rows).
     ``round_w`` rounds W_p0 and A (the wB / wC images), ``round_act`` the GEMM inputs [row | counts], r_e and r_p.
     ``lite`` (bool [bs]): pairs the tail takes without a pairwise branch -- w_dot . ReLU(A_e r_e + bC_empty) + b_dot
     (lpf_tail_chain_rows_perm_*: a workgroup of pairs without selected nodes).  ``d_rows``: a bound on the rows'
-    error carried in (a bf16 attention upstream).  Returns dict logit, r_p, d_logit (flip bound), n_flag, n_elem."""
+    error carried in (a bf16 attention upstream).  ``ln_eps``: the epsilon of LN_B (near-miss: 0).  Returns dict logit, r_p, d_logit (flip bound), n_flag, n_elem."""
     rows, r_e = _f64(rows), _f64(r_e)
     x = np.concatenate([rows, _f64(feats_cnt)], axis=1)
     d = rows.shape[1]
@@ -260,7 +270,7 @@ def tail_ref(rows, feats_cnt, r_e, t, *, round_act=False, round_w=False, lite=No
     else:
         re_, dre = r_e, np.zeros_like(r_e)
     v = x @ w_p0.T + _f64(t["b_p0"])
-    y, xhat, sd = layer_norm(v, _f64(t["lnB_g"]), _f64(t["lnB_b"]))
+    y, xhat, sd = layer_norm(v, _f64(t["lnB_g"]), _f64(t["lnB_b"]), ln_eps)
     r_p = np.maximum(y, 0.0)
     drp = ln_bound(np.abs(dx) @ np.abs(w_p0).T, xhat, sd, _f64(t["lnB_g"]))
     if round_act:
@@ -283,13 +293,15 @@ def tail_ref(rows, feats_cnt, r_e, t, *, round_act=False, round_w=False, lite=No
 
 # ------------------------------------------------------------------------------------------------- encoder
 def encoder_ref(x, rowptr, col, val, layers, *, residual, relu, final_ln, round_x=False, rounder=rne_bf16,
-                dup_part=None):
+                dup_part=None, f32_unit=None):
     """GCN encoder as the fused layer kernel computes it:  y = LN(ReLU?)(A_hat g(X) W^T + b), X <- X + y (residual),
     gnn_norm after the last layer; g = bf16 rounding of the gathered layer input with ``round_x`` (layer 0: the
     features, a torch cast -- no flips; later layers: the kernel rounds its own fp32 output -- flagged, window
     D 2^-24 max(|x|, row RMS / sqrt(D))).  layers: list of (W [D, D], bias, ln_g or None, ln_b or None);
     final_ln: (g, b).  ``dup_part``: (layer, row, lo, hi) -- entries [lo, hi) of that row counted twice (near-miss of a
-    hub-part bug).  Returns dict out, d_out (flip bound), n_flag, n_elem."""
+    hub-part bug).  ``f32_unit``: a layer's own fp32 error, f32_unit (|A_hat| |X| |W|^T + |b|), is added to the bound
+    before its LayerNorm and carried like the rest (tests/f32_error_model.py).  Returns dict out, d_out (flip bound),
+    n_flag, n_elem."""
     x = _f64(x)
     rowptr, col, val = (np.asarray(a) for a in (rowptr, col, val))
     n = rowptr.size - 1
@@ -319,6 +331,8 @@ def encoder_ref(x, rowptr, col, val, layers, *, residual, relu, final_ln, round_
         dagg = (a_abs @ torch.from_numpy(dg)).numpy()
         v = agg @ w.T + _f64(b)
         dv = dagg @ np.abs(w).T
+        if f32_unit is not None:
+            dv = dv + f32_unit * ((a_abs @ torch.from_numpy(np.abs(xr))).numpy() @ np.abs(w).T + np.abs(_f64(b)))
         if g is not None:
             v, xhat, sd = layer_norm(v, _f64(g), _f64(be))
             dv = ln_bound(dv, xhat, sd, _f64(g))

@@ -22,23 +22,17 @@ fp32 re-association over the producing chain: C_ATT = 4 D (D-term products for k
 times 4 for the LayerNorm's 1 / sigma on rows whose sigma is >= 1/4 of their largest element), C_LOGIT = 16 D (two
 chained products of <= 2 D + 4 terms and two LayerNorms behind the rows), C_ENC = 4 D per layer.
 """
-import collections
-
 import numpy as np
 import pytest
 import torch
 
-import lpformer_amd
-from lpformer_amd import _lib
-from lpformer_amd import data as D
 from tests import bf16_reference as R
+from tests.scoring_harness import DEV, Reach, _DEFAULTS, _inputs, _lite, _np, _setup, knobs
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 EPS23 = 2.0 ** -23
 OLD_ATT_TOL, OLD_ENC_TOL = 5e-3, 3e-2          # what the bf16 modes were held to against the fp32 path
 FLAG_FRACTION = 5e-3
-N_ISO = 20
 
 ATT_ENTRIES = ("lpf_pair_attention_rows4_zbf16", "lpf_pair_attention_rows_zbf16", "lpf_pair_attention_rows_perm_zbf16",
                "lpf_pair_attention_flip_zbf16", "lpf_pair_attention_fused_bf16")
@@ -46,107 +40,9 @@ TAIL_ENTRIES = ("lpf_tail_chain_rows_bf16", "lpf_tail_chain_rows_perm_bf16", "lp
 ENC_ENTRIES = ("lpf_gcn_layer_fused_bf16", "lpf_spmm_row_parts_bf16p")
 
 
-class Reach:
-    """Call counts of the watched C entry points (wrappers on the ``_lib.hip()`` object)."""
-
-    def __init__(self, monkeypatch, names):
-        self.calls = collections.Counter()
-        lib = _lib.hip()
-        for nm in names:
-            fn = getattr(lib, nm)
-
-            def wrap(*a, _fn=fn, _nm=nm):
-                self.calls[_nm] += 1
-                return _fn(*a)
-            monkeypatch.setattr(lib, nm, wrap)
-
-    def ran(self, fn):
-        before = dict(self.calls)
-        out = fn()
-        torch.cuda.synchronize()
-        return out, {k for k, v in self.calls.items() if v > before.get(k, 0)}
-
-
-def _graph(seed, n=2000, weighted=False):
-    """Heavy-tailed graph with two hubs (700 / 650 neighbours: their pair selects > 512 nodes, the hub rows of the
-    encoder are cut into parts) and N_ISO isolated nodes (their pairs select nothing)."""
-    rng = np.random.default_rng(seed)
-    ei, w = D.chung_lu_graph(n, 11000, gamma=2.1, seed=seed, max_weight=5 if weighted else 0)
-    star = np.concatenate([np.stack([np.zeros(700, np.int64), rng.choice(np.arange(2, n - N_ISO), 700, replace=False)]),
-                           np.stack([np.ones(650, np.int64), rng.choice(np.arange(2, n - N_ISO), 650, replace=False)])], 1)
-    allp = np.concatenate([ei, star, star[::-1]], axis=1)
-    allw = None if w is None else np.concatenate([w, np.ones(2 * star.shape[1], np.float32)])
-    keep = (allp[0] < n - N_ISO) & (allp[1] < n - N_ISO)
-    allp, allw = allp[:, keep], (None if allw is None else allw[keep])
-    _, u = np.unique(allp[0] * n + allp[1], return_index=True)
-    return allp[:, u], (None if allw is None else allw[u])
-
-
-def _setup(dim, mode, seed=0, layers=1, residual=False, weighted=False, f_in=40, bs=700):
-    n = 2000
-    ei, w = _graph(seed, n, weighted)
-    rng = np.random.default_rng(seed + 1)
-    x = rng.standard_normal((n, f_in)).astype(np.float32)
-    th = {"all": (0.0, 0.0, 1e-3), "1-hop": (0.0, 0.0, 1.0), "cn": (0.0, 1.0, 1.0)}[mode]
-    data = D.build_data(ei, x, n, edge_weight=w, ppr=lpformer_amd.calc_ppr(ei, n, 0.15, 1e-4))
-    args = D.train_args_for(dict(thresholds=th, dim=dim, gnn_layers=layers, residual=residual))
-    torch.manual_seed(seed)
-    model = lpformer_amd.LinkTransformer(args, data, device=DEV).to(DEV).eval()
-    score = lpformer_amd.mlp_score(2 * dim, 2 * dim, 1, 2).to(DEV).eval()
-    with torch.no_grad():
-        for p in list(model.parameters()) + list(score.parameters()):
-            if p.dim() == 1:
-                p.add_(0.1 * torch.randn_like(p))
-    batch = D.sample_pairs(ei, n, bs, seed=seed + 2, frac_edges=0.3)
-    iso = np.arange(n - N_ISO, n)
-    batch[:, :8] = np.array([[0, 1, 0, 5, 7, 7, 0, iso[0]],
-                             [1, 0, 0, 5, 9, 9, 3, iso[0]]])       # hubs, a == b, duplicates
-    batch[:, 8:110] = rng.choice(iso, (2, 102))                     # pairs that select nothing: > 64 of them
-    return model, score, data, torch.from_numpy(batch).to(DEV)
-
-
-def _np(t):
-    return t.detach().float().cpu().numpy()
-
-
-def _inputs(model, score, tb, h):
-    """What the restatement may take: selection records, x_node, fp32 Z and q, the fp32 fold tables."""
-    model._fold_memo = None
-    w = model._fold()
-    z = model._node_keys(h, w)
-    q = model._pair_q(tb, h, w)
-    sel = [None if s is None else tuple(_np(a) if a.dtype.is_floating_point else a.cpu().numpy() for a in s)
-           for s in model.compute_node_mask(tb)]
-    layer, pw, ew = model.att_layers[0], model.pairwise_lin, model.elementwise_lin
-    a, c, _ = model._score_fold(score)
-    tt = model._tail_tables(score, a, c)
-    d, pd = model.dim, model.dim + model.count_dim
-    tabs = {"w_p0": pw.linears[0].weight, "b_p0": pw.linears[0].bias, "lnB_g": pw.norm.weight, "lnB_b": pw.norm.bias,
-            "A": a[:, :d + pd], "c": c, "w_dot": score.lins[1].weight.reshape(-1), "b_dot": score.lins[1].bias,
-            "bC_empty": tt["bC_empty"]}
-    r_e = R.elementwise_hidden(_np(h), tb.cpu().numpy(), ew.linears[0].weight, ew.linears[0].bias, ew.norm.weight,
-                               ew.norm.bias)
-    return {"w": {k: _np(v) for k, v in w.items() if k in ("wfold", "bfold", "att", "pe_tab", "pe_stat")},
-            "z": _np(z), "q": _np(q), "sel": sel, "tabs": {k: _np(v) for k, v in tabs.items()}, "r_e": r_e,
-            "att_bias": _np(layer.att.bias), "ln": (_np(layer.post_att_norm.weight), _np(layer.post_att_norm.bias)),
-            "bs": tb.shape[1]}
-
-
 def _att(inp, fused, **kw):
     return R.attention_ref(inp["sel"], inp["z"], inp["q"], inp["w"], inp["att_bias"], *inp["ln"], inp["bs"],
                            round_z=True, round_h=fused, round_wfold=fused, **kw)
-
-
-def _lite(counts, bs):
-    """Pairs a lpf_tail_chain_rows_perm_* launch scores without their pairwise branch: pairs without selected nodes sit
-    at positions bs - 1 - i of its order (i-th of them ascending); a 64-pair workgroup is 'lite' when it starts at or
-    behind the number of pairs with selected nodes."""
-    empty = counts.sum(axis=1) == 0
-    n_full = int((~empty).sum())
-    lite = np.zeros(bs, bool)
-    pos = bs - 1 - np.arange(int(empty.sum()))
-    lite[np.flatnonzero(empty)] = (pos // 64) * 64 >= n_full
-    return lite
 
 
 def _check(name, got, ref, bound, c, d):
@@ -161,16 +57,7 @@ def _check(name, got, ref, bound, c, d):
 
 
 # ------------------------------------------------------------------------------------------------- attention
-KNOBS = {   # name -> (model settings, entry point of calc_pairwise, entry points of score_pairs)
-    "rows4": (dict(attention_impl="flip"), "lpf_pair_attention_rows4_zbf16", {"lpf_pair_attention_rows4_zbf16"}),
-    "rows": (dict(attention_impl="flip", use_select_index=False, tail_skip_empty=False),
-             "lpf_pair_attention_rows_zbf16", {"lpf_pair_attention_rows_zbf16"}),
-    "rows_perm": (dict(attention_impl="flip", use_select_index=False), "lpf_pair_attention_rows_zbf16",
-                  {"lpf_pair_attention_rows_perm_zbf16"}),
-    "flip": (dict(attention_impl="flip", attention_rows=False), "lpf_pair_attention_flip_zbf16",
-             {"lpf_pair_attention_flip_zbf16"}),
-    "mfma": (dict(attention_impl="mfma"), "lpf_pair_attention_fused_bf16", {"lpf_pair_attention_fused_bf16"}),
-}
+KNOBS = knobs("bf16")   # name -> (model settings, entry point of calc_pairwise, entry points of score_pairs)
 
 
 @pytest.mark.parametrize("dim,mode", [(64, "all"), (128, "all"), (256, "all"), (128, "1-hop"), (64, "cn")])
@@ -231,9 +118,6 @@ def test_bf16_attention_matches_rounded_reference(dim, mode, monkeypatch):
             setattr(model, k, _DEFAULTS[k])
     assert seen >= set(ATT_ENTRIES)
     assert not seen & set(TAIL_ENTRIES)          # (tail_precision stayed fp32)
-
-
-_DEFAULTS = dict(attention_impl="auto", use_select_index=True, tail_skip_empty=True, attention_rows=True)
 
 
 # ------------------------------------------------------------------------------------------------- tail
