@@ -313,6 +313,21 @@ int lpf_select4(int64_t bs, const int64_t *batch, int64_t batch_ld, int64_t n_no
                 int64_t *ctl, void *pair_tab, int32_t *blk_cnt, void *blk_types, void *entries, int64_t ent_cap,
                 int32_t threads, void *stream);
 
+/* lpf_select4 that ALSO leaves the attention's per-pair query q_out[p, :q_dim] = q_tab[a_p] + q_tab[b_p] (that operand
+ * order, = lpf_pair_gather_f32(sum) and lpf_dense_chain_side_f32; layers.py:212-215) for the pairs that KEPT at least one
+ * entry -- the only pairs whose query lpf_pair_attention_rows4_* reads.  The rows of pairs without entries, and every row of
+ * a workgroup that did not fit the entry buffer, are NOT written.  The workgroup that typed a block of pairs writes their
+ * rows at its end, when the counts are final: no launch and no pass over memory for the other pairs' rows.
+ *   q_tab  float [n_nodes, ld_q_tab] per-node table, q_out float [bs, ld_q_out]; q_dim % 4 == 0, q_dim <= 128, rows
+ *          16-byte aligned.  q_out NULL: lpf_select4.
+ * Added within ABI 16: the addition changes no existing symbol, so LPF_ABI_VERSION stays. */
+int lpf_select4_q(int64_t bs, const int64_t *batch, int64_t batch_ld, int64_t n_nodes, const void *node_rec,
+                  const void *adj_cv, const void *a1_cv, const void *px_cv, const void *t0_cv, const void *u_cv,
+                  const void *mini, int32_t mode_cn, int32_t use_px, float th_cn, float th_1hop, float th_non1hop,
+                  int64_t *ctl, void *pair_tab, int32_t *blk_cnt, void *blk_types, void *entries, int64_t ent_cap,
+                  int32_t threads, const float *q_tab, int64_t ld_q_tab, float *q_out, int64_t ld_q_out, int32_t q_dim,
+                  void *stream);
+
 /* lpf_select4's result in the TYPE-MAJOR form of lpf_select3_run (what the matrix-core attention, the record-merging tail
  * and lpf_select_export read): type_ptr int32[3][bs + 1] per-type segment pointers and three regions of `ent_cap` 16-byte
  * records {pair | from_N(b) << 31, node, pa, pb} ordered by (pair, candidate slot) -- same sets, same values, same order
@@ -664,6 +679,24 @@ int lpf_tail_chain_rows_perm_bf16(int64_t M, int32_t D, int32_t n_counts, const 
                                   const float *w_dot, const float *b_dot, const int64_t *sel_ctl, const int32_t *perm,
                                   const int64_t *n_full, const float *bC_empty, const float *row_empty, float *logit,
                                   float *prob, void *stream);
+/* lpf_tail_chain_rows_perm_f32 that computes r_e itself: r_e[m] = ReLU(LayerNorm(W_e0 (X[a_m] * X[b_m]) + b_e0)), the
+ * first layer of elementwise_lin (other_models.py:125-138), is a stage of the tail's own workgroups ("stage E": the gather
+ * and arithmetic of lpf_dense_chain_f32 with in_mode 1, operation for operation), handed to the score head through LDS --
+ * no r_e buffer, no launch of the elementwise branch.  The scores are bitwise those of lpf_dense_chain_f32 (-> r_e) +
+ * lpf_tail_chain_rows_perm_f32.
+ *   X float [n_rows, ldx] node table, batch int64 [2][batch_ld] (ids outside [0, n_rows) read row 0), wE_packed the packed
+ *   image of W_e0 [D, D] (fold.dense_chain_tables: w1p), bE / lnE_g / lnE_b float [D].
+ * wE_packed NULL: r_e is read from memory, exactly lpf_tail_chain_rows_perm_f32 (X, batch and the E tables are then
+ * ignored).  With wE_packed, r_e is ignored.  Built for D = 128; other widths return LPF_ERR_UNSUPPORTED.
+ * Added within ABI 16: the addition changes no existing symbol, so LPF_ABI_VERSION stays. */
+int lpf_tail_chain_rows_perm_ew_f32(int64_t M, int32_t D, int32_t n_counts, const float *rows, int64_t ldrows,
+                                    const float *wB_packed, const float *bB, const float *lnB_g, const float *lnB_b,
+                                    const float *r_e, int64_t ldre, const float *wC_packed, const float *bC,
+                                    const float *w_dot, const float *b_dot, const int64_t *sel_ctl, const int32_t *perm,
+                                    const int64_t *n_full, const float *bC_empty, const float *row_empty,
+                                    const float *X, int64_t ldx, const int64_t *batch, int64_t batch_ld, int64_t n_rows,
+                                    const float *wE_packed, const float *bE, const float *lnE_g, const float *lnE_b,
+                                    float *logit, float *prob, void *stream);
 
 /* logit[i] = dot(A[i,:], w) + b ; prob[i] = sigmoid(logit[i])  (mlp_score last layer, other_models.py:178-179).
  * logit or prob may be NULL. */

@@ -26,6 +26,8 @@
 // Result: entries {pair | type << 29 | from_N(b) << 31, node, pa, pb}; pair_tab[pair] = {start, n_cn, n_1hop, n_far};
 // blk_cnt[block] = {entries, pairs with entries} of the block (the attention kernel splits its work by it).  Deterministic up to the block
 // bases: every consumer addresses entries through pair_tab, so scores do not depend on where a block landed.
+// Optional (lpf_select4_q): the workgroup also leaves the attention's query q[pair] = Y[a] + Y[b] for its pairs WITH entries
+// -- at its end, when it knows which those are; the attention reads no other pair's query.
 #include "walk_common.h"
 
 namespace {
@@ -60,6 +62,11 @@ struct Args4 {
     int4 *blk_types;     // optional [ceil(bs / 64)]: {common neighbours, one-hop, >1-hop, 0} kept per block (lpf_select4_regions)
     int4 *entries;       // [ent_cap]
     int64_t ent_cap;
+    // optional query epilogue (lpf_select4_q; q_out NULL: none): q_out[p] = q_tab[a_p] + q_tab[b_p] for the pairs that kept
+    // an entry, written by the workgroup that typed them
+    const float *q_tab; int64_t ld_q_tab;
+    float *q_out; int64_t ld_q_out;
+    int32_t q_dim;
 };
 
 // NB: blocks of 64 pairs a workgroup takes together (one planning wavefront each; their slots form one space, their
@@ -300,9 +307,56 @@ __global__ __launch_bounds__(NTH, 4) void select4_kernel(const Args4 A) {
         }
     }
     S4_STAMP(8);    // entries written (issued), further batches
+    // (LDS-only barrier: what follows reads LDS -- the counts and, in the query epilogue, the descriptors' ids -- and a
+    //  kernel INPUT -- the query table --, nothing another wavefront wrote to global memory)
     lpf_lds_barrier();
     S4_STAMP(9);
     const bool ovf = S > 0 && L.ovf != 0;
+    // ---- query epilogue (lpf_select4_q): the attention reads a pair's query only when the pair has entries (pair_rows.hip:
+    //      q_row is called for pairs of entries), and only now is it known which pairs do.  The pairs with entries of every
+    //      block of 64 are ranked by ballot and dealt to all wavefronts two at a time -- a 512-byte row per 32 lanes --; a
+    //      wavefront takes the ids of its pairs from their descriptors (LDS), requests both table rows of all of them
+    //      here, and adds and stores them behind the table write-out below: ONE round trip behind everything else.
+    constexpr int QU = 32 / WAVES, NU = NB * QU;   // units of two pairs per wavefront: per block, in all
+    static_assert(32 % WAVES == 0, "a block's 32 units are dealt wavefront by wavefront");
+    const int hl = lane & 31, hh = lane >> 5;
+    const bool qcol = A.q_out && 4 * hl < A.q_dim;
+    int64_t qp[NU];
+    float4 qa[NU], qb[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) qp[u] = -1;
+    if (A.q_out) {      // (workgroup-uniform)
+#pragma unroll
+        for (int q = 0; q < NB; ++q) {
+            const int jq = S4_PAIRS * q + lane;
+            const int4 cq = *reinterpret_cast<const int4 *>(L.pcnt[jq]);
+            const bool ne = jq < np && !ovf && cq.x + cq.y + cq.z > 0;
+            const uint64_t bq = __ballot(ne);
+            const int nq = __popcll(bq), rank = __popcll(bq & lt_mask);
+#pragma unroll
+            for (int k = 0; k < QU; ++k) {
+                const int u = q * QU + k;
+                const int r0 = 2 * (wave + k * WAVES);     // ranks r0 (lower 32 lanes) and r0 + 1 (upper) of the block
+                qa[u] = make_float4(0.f, 0.f, 0.f, 0.f); qb[u] = qa[u];
+                if (r0 < nq) {                              // (wave-uniform)
+                    const uint64_t m0 = __ballot(ne && rank == r0), m1 = __ballot(ne && rank == r0 + 1);
+                    const uint64_t mine = hh ? m1 : m0;
+                    if (mine) {
+                        const int jm = S4_PAIRS * q + __builtin_ctzll(mine);
+                        // (a pair with entries went through build_desc: its ids are in the table; checked all the same)
+                        const int64_t ia = L.dsc[jm].a, ib = L.dsc[jm].b;
+                        if ((uint64_t)ia < (uint64_t)A.n_nodes && (uint64_t)ib < (uint64_t)A.n_nodes) {
+                            qp[u] = p0 + jm;
+                            if (qcol) {
+                                qa[u] = *reinterpret_cast<const float4 *>(A.q_tab + ia * A.ld_q_tab + 4 * hl);
+                                qb[u] = *reinterpret_cast<const float4 *>(A.q_tab + ib * A.ld_q_tab + 4 * hl);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
     if (wave < NB) {    // block q's {entries, pairs with entries}: lane = pair
         const int j = S4_PAIRS * wave + lane;
         const int4 cc = *reinterpret_cast<const int4 *>(L.pcnt[j]);
@@ -328,6 +382,13 @@ __global__ __launch_bounds__(NTH, 4) void select4_kernel(const Args4 A) {
         // (a workgroup that does not fit leaves empty pairs -- nothing is read past the buffer -- and raises the sticky bit:
         //  the scores of the batch come out as NaN and the caller sizes the workspace again)
         A.pair_tab[p0 + tid] = ovf ? make_int4(0, 0, 0, 0) : make_int4((int32_t)(L.base + c.w), c.x, c.y, c.z);
+    }
+    if (A.q_out) {      // q[p] = Y[a] + Y[b], that operand order (= lpf_pair_gather_f32 and the side gather of dense_chain.hip)
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+            if (qp[u] >= 0 && qcol)
+                *reinterpret_cast<float4 *>(A.q_out + qp[u] * A.ld_q_out + 4 * hl) =
+                    make_float4(qa[u].x + qb[u].x, qa[u].y + qb[u].y, qa[u].z + qb[u].z, qa[u].w + qb[u].w);
     }
     if (tid == 0) {
         if (ovf) atomicOr(reinterpret_cast<unsigned long long *>(A.ctl + CTL_ERR), (unsigned long long)LPF_SELECT_ERR_ENTRY_CAP);
@@ -364,17 +425,21 @@ extern "C" int lpf_select4_set_stamps(void *buf) {
 #endif
 
 /* ---- C ABI ---------------------------------------------------------------------------------------------------- */
-extern "C" int lpf_select4(int64_t bs, const int64_t *batch, int64_t batch_ld, int64_t n_nodes, const void *node_rec,
-                           const void *adj_cv, const void *a1_cv, const void *px_cv, const void *t0_cv, const void *u_cv,
-                           const void *mini, int32_t mode_cn, int32_t use_px, float th_cn, float th_1hop,
-                           float th_non1hop, int64_t *ctl, void *pair_tab, int32_t *blk_cnt, void *blk_types,
-                           void *entries, int64_t ent_cap, int32_t threads, void *stream) {
+extern "C" int lpf_select4_q(int64_t bs, const int64_t *batch, int64_t batch_ld, int64_t n_nodes, const void *node_rec,
+                             const void *adj_cv, const void *a1_cv, const void *px_cv, const void *t0_cv, const void *u_cv,
+                             const void *mini, int32_t mode_cn, int32_t use_px, float th_cn, float th_1hop,
+                             float th_non1hop, int64_t *ctl, void *pair_tab, int32_t *blk_cnt, void *blk_types,
+                             void *entries, int64_t ent_cap, int32_t threads, const float *q_tab, int64_t ld_q_tab,
+                             float *q_out, int64_t ld_q_out, int32_t q_dim, void *stream) {
     if (bs == 0) return LPF_OK;
     LPF_REQUIRE(bs > 0 && bs < (1ll << 29) && batch && batch_ld >= bs && n_nodes > 0 && node_rec && adj_cv && a1_cv &&
                 (px_cv || !use_px) && u_cv && mini && ctl && pair_tab && blk_cnt && entries && ent_cap > 0 &&
                 ent_cap < (1ll << 31) && lpf_aligned16(node_rec) && lpf_aligned16(u_cv) && lpf_aligned16(mini) &&
                 lpf_aligned16(pair_tab) && lpf_aligned16(entries) && (reinterpret_cast<uintptr_t>(blk_cnt) & 7) == 0 &&
                 lpf_aligned16(blk_types));
+    LPF_REQUIRE(!q_out || (q_tab && q_dim > 0 && (q_dim & 3) == 0 && ld_q_tab >= q_dim && ld_q_out >= q_dim &&
+                           (ld_q_tab & 3) == 0 && (ld_q_out & 3) == 0 && lpf_aligned16(q_tab) && lpf_aligned16(q_out)));
+    if (q_out && q_dim > 128) return LPF_ERR_UNSUPPORTED;   // (a row per 32 lanes)
     Args4 a;
     a.bs = bs; a.batch = batch; a.batch_ld = batch_ld; a.n_nodes = n_nodes;
     a.rec = static_cast<const NodeRec *>(node_rec);
@@ -385,6 +450,7 @@ extern "C" int lpf_select4(int64_t bs, const int64_t *batch, int64_t batch_ld, i
     a.ctl = ctl; a.pair_tab = static_cast<int4 *>(pair_tab); a.blk_cnt = blk_cnt;
     a.blk_types = static_cast<int4 *>(blk_types);
     a.entries = static_cast<int4 *>(entries); a.ent_cap = ent_cap;
+    a.q_tab = q_tab; a.ld_q_tab = ld_q_tab; a.q_out = q_out; a.ld_q_out = ld_q_out; a.q_dim = q_dim;
     const int64_t nb = (bs + S4_PAIRS - 1) / S4_PAIRS;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // threads = workgroup size + 4096 * (blocks of 64 pairs per workgroup - 1); 0: the default -- 1,024 threads and two
@@ -406,6 +472,16 @@ extern "C" int lpf_select4(int64_t bs, const int64_t *batch, int64_t batch_ld, i
     else return LPF_ERR_INVALID;
     LPF_CHECK_LAUNCH();
     return LPF_OK;
+}
+
+extern "C" int lpf_select4(int64_t bs, const int64_t *batch, int64_t batch_ld, int64_t n_nodes, const void *node_rec,
+                           const void *adj_cv, const void *a1_cv, const void *px_cv, const void *t0_cv, const void *u_cv,
+                           const void *mini, int32_t mode_cn, int32_t use_px, float th_cn, float th_1hop,
+                           float th_non1hop, int64_t *ctl, void *pair_tab, int32_t *blk_cnt, void *blk_types,
+                           void *entries, int64_t ent_cap, int32_t threads, void *stream) {
+    return lpf_select4_q(bs, batch, batch_ld, n_nodes, node_rec, adj_cv, a1_cv, px_cv, t0_cv, u_cv, mini, mode_cn, use_px,
+                         th_cn, th_1hop, th_non1hop, ctl, pair_tab, blk_cnt, blk_types, entries, ent_cap, threads, nullptr,
+                         0, nullptr, 0, 0, stream);
 }
 
 /* ---- pair-major -> type-major ---------------------------------------------------------------------------------- */

@@ -11,6 +11,14 @@
 // count features), stage C starts with k-groups read from global memory (r_e, produced on the side stream by the
 // elementwise branch).  Against three separate launches this removes two launch ramps and the round trips of the
 // attention output and of r_p through HBM.
+//
+// Stage E (rows + perm form, fp32, D = 128: lpf_tail_chain_rows_perm_ew_f32) puts the elementwise branch in front:
+//   E  r_e = ReLU(LayerNorm( W_e0 (x_a * x_b) + b_e0 ))                  first layer of elementwise_lin
+// with the gathered B operand and the arithmetic of dense_chain.hip (in_mode 1), operation for operation.  r_e goes to
+// the hidden tiles and stage C's r_e half runs directly behind it -- the tiles are free again before stage A writes
+// them, so LDS does not grow --; its accumulators then live across stages A and B.  Order inside a workgroup:
+// E -> C over r_e -> (64 pairs without selected nodes: epilogue, done) -> A -> B -> C over r_p -> epilogue.  Stage C
+// sums in the order it always did (r_e k-groups first), so the scores are bitwise those of the separate launches.
 #include <type_traits>
 
 #include "lpf_common.h"
@@ -60,6 +68,11 @@ struct TailArgs {
     // ... and a pair without selected nodes in a MIXED workgroup takes its (constant) row from here and zero counts: the
     // attention kernel that leaves the order does not write rows for such pairs
     const float *row_empty;         // [NA]
+    // stage E (EW instantiation, wE != nullptr): r_e is not read from `re` but computed from the node table, X[a] * X[b]
+    // gathered through batch[0][m], batch[1][m] (ids outside [0, n_rows) read row 0, as in dense_chain.hip)
+    const float *X; int64_t ldX;
+    const int64_t *batch; int64_t batch_ld, n_rows;
+    const float *wE, *bE, *lnE_g, *lnE_b;
 };
 
 constexpr int tc_per_thread(int ntp) { return (ntp * 64 + TC_THREADS - 1) / TC_THREADS; }
@@ -161,8 +174,10 @@ __device__ __forceinline__ void tc_layernorm(f32x4 (&acc)[TPW], int fbase, int n
 #ifdef TC_STAMPS
 __device__ uint64_t *tc_stamp_buf = nullptr;
 #define TC_STAMP(k) do { if (lane == 0) st_t[k] = wall_clock64(); } while (0)
-#define TC_STAMPS_OUT(kind) do { if (lane == 0 && tc_stamp_buf) { uint64_t *o__ = tc_stamp_buf + ((int64_t)blockIdx.x * TC_WAVES + wave) * 8; \
-        for (int k__ = 0; k__ < 7; ++k__) o__[k__] = st_t[k__]; o__[7] = (kind); } } while (0)
+#define TC_STAMPS_OUT(kind) do { if (lane == 0 && tc_stamp_buf) { uint64_t *o__ = tc_stamp_buf + ((int64_t)blockIdx.x * TC_WAVES + wave) * 16; \
+        for (int k__ = 0; k__ < 8; ++k__) o__[k__] = st_t[k__]; o__[15] = (kind); } } while (0)
+// (16 words per wavefront: marks 0-6 as they always were, 7 = stage E done -- with it mark 4, C's r_e k-groups, comes
+//  BEFORE mark 1 --, word 15 = the kind)
 #else
 #define TC_STAMP(k) do { } while (0)
 #define TC_STAMPS_OUT(kind) do { } while (0)
@@ -183,7 +198,8 @@ struct TcShape {
 // (D = 256: 32 output tiles of the score head -- 16 accumulators per lane in stage C alone --, one workgroup per CU with
 //  twice the registers)
 // WM: how the two GEMMs run -- 0 fp32 weights and MFMAs, 1 bf16 weights and activations (throughput mode)
-template <int NTA, int NTB, int NTC, int WM = 0, bool ROWS = false>
+// EW: stage E in front (rows + perm form, fp32)
+template <int NTA, int NTB, int NTC, int WM = 0, bool ROWS = false, bool EW = false>
 __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 : 3)) void tail_chain_kernel(const TailArgs A) {
     using S = TcShape<NTA, NTB, NTC>;
     constexpr bool WB = WM != 0;
@@ -224,11 +240,75 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     bool no_sel = false;        // (rows mode with an order: this pair has no selected nodes)
     if constexpr (ROWS) no_sel = A.perm && A.row_empty && (live ? pos : A.M - 1) >= *A.n_full;
 
+    f32x4 accC[TPWC];           // stage C's accumulators (with stage E they are filled first and live across A and B)
+    if constexpr (EW) {
+        static_assert(ROWS && WM == 0 && S::PA == 1 && NTPA == NTA && NGE % 2 == 0 && 2 * tc_stage_stride(NTPA) <= S::SLAB &&
+                          tc_stage_stride(2 * NTPA) == 2 * tc_stage_stride(NTPA), "stage E: the fp32 rows form at D = 128");
+        // ------------------------------------------------------------------ stage E: first layer of elementwise_lin
+        // dense_chain.hip's layer 1 with in_mode 1: the B operand of k-group kg is X[a][16 kg + 4 q ..] * X[b][..]; a lane's
+        // sixteen 16-byte pieces of the two rows are requested at once, in front of the first k-group (the kernel's
+        // other stages need the registers only later), so the gather is one round trip, not one per k-group
+        int64_t ra = A.batch[mm], rb = A.batch[A.batch_ld + mm];
+        if ((uint64_t)ra >= (uint64_t)A.n_rows) ra = 0;
+        if ((uint64_t)rb >= (uint64_t)A.n_rows) rb = 0;
+        const float *xa = A.X + ra * A.ldX + 4 * q, *xb = A.X + rb * A.ldX + 4 * q;
+        f32x4 accE[TPWA];
+#pragma unroll
+        for (int c = 0; c < TPWA; ++c) accE[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        // (two k-groups per weight stage and barrier: a k-group of this layer is 512 float4, a slab holds 1,024; the
+        //  k-groups still reach an accumulator in ascending order)
+        WT wrE[2];
+        tc_load<2, 2 * NTPA>(wrE, A.wE, 0, tid);
+        f32x4 xra[NGE], xrb[NGE];
+#pragma unroll
+        for (int kg = 0; kg < NGE; ++kg) {
+            xra[kg] = *reinterpret_cast<const f32x4 *>(xa + 16 * kg);
+            xrb[kg] = *reinterpret_cast<const f32x4 *>(xb + 16 * kg);
+        }
+#pragma unroll
+        for (int kg = 0; kg < NGE; kg += 2) {
+            const f32x4 bv0 = xra[kg] * xrb[kg], bv1 = xra[kg + 1] * xrb[kg + 1];
+            WT *lw = reinterpret_cast<WT *>(lds) + buf * S::SLAB;
+            tc_store<2>(wrE, lw, tid);
+            __syncthreads();
+            if (kg + 2 < NGE) tc_load<2, 2 * NTPA>(wrE, A.wE, kg / 2 + 1, tid);
+            tc_mfma<TPWA>(accE, lw + (half * TPWA) * 64 + lane, bv0);
+            tc_mfma<TPWA>(accE, lw + tc_stage_stride(NTPA) + (half * TPWA) * 64 + lane, bv1);
+            buf ^= 1;
+        }
+        WT wrCe[S::PC];
+        tc_load<S::PC, NTPC>(wrCe, A.wC, 0, tid);  // stage C's first weights fly during the epilogue
+        {   // bias -> LayerNorm -> ReLU: dense_chain.hip's epilogue 1, same operations in the same order
+            const int fbase = 16 * half * TPWA + 4 * q;
+#pragma unroll
+            for (int c = 0; c < TPWA; ++c) accE[c] += *reinterpret_cast<const f32x4 *>(A.bE + fbase + 16 * c);
+            tc_layernorm<TPWA>(accE, fbase, A.NA, A.lnE_g, A.lnE_b, half, q, my_x, peer_x, true);
+#pragma unroll
+            for (int c = 0; c < TPWA; ++c) my_hid[(half * TPWA + c) * 64] = accE[c];
+        }
+        TC_STAMP(7);
+        // ---- stage C over the r_e k-groups, r_e straight from LDS
+#pragma unroll
+        for (int c = 0; c < TPWC; ++c) accC[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int kg = 0; kg < NGE; ++kg) {
+            WT *lw = reinterpret_cast<WT *>(lds) + buf * S::SLAB;
+            tc_store<S::PC>(wrCe, lw, tid);
+            __syncthreads();  // (kg == 0: also publishes stage E's hidden tiles)
+            if (kg + 1 < NGE) tc_load<S::PC, NTPC>(wrCe, A.wC, kg + 1, tid);
+            tc_mfma<TPWC>(accC, lw + (half * TPWC) * 64 + lane, my_hid[kg * 64]);
+            buf ^= 1;
+        }
+        TC_STAMP(4);
+        if (!lite) __syncthreads();   // every wave has read r_e: stage A may write the hidden tiles  (workgroup-uniform)
+    }
+
     if constexpr (ROWS) {
         if (lite) {
             // ---- 64 pairs without selected nodes: score = w_dot . ReLU(A_e r_e + bC_empty) + b_dot -- stage C over the
             //      r_e k-groups alone (35 % of the matrix work of a full workgroup), nothing else
-            f32x4 acc[TPWC];
+            f32x4 (&acc)[TPWC] = accC;
+            if constexpr (!EW) {
 #pragma unroll
             for (int c = 0; c < TPWC; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
             WT wr[S::PC];
@@ -248,6 +328,7 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
                 tc_mfma<TPWC>(acc, lw + (half * TPWC) * 64 + lane, bv);
                 buf ^= 1;
             }
+            }   // (!EW)
             const int fbase = 16 * half * TPWC + 4 * q;
             float d = 0.f;
 #pragma unroll
@@ -442,9 +523,10 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     }
     TC_STAMP(2);
     WT wrC[S::PC];
-    tc_load<S::PC, NTPC>(wrC, A.wC, 0, tid);
-    const float *rer = A.re + mm * A.ldre + 4 * q;
-    f32x4 xr = *reinterpret_cast<const f32x4 *>(rer);  // stage C's first input group
+    tc_load<S::PC, NTPC>(wrC, A.wC, EW ? NGE : 0, tid);   // (stage E form: C's r_e k-groups are done, the r_p groups follow)
+    const float *rer = EW ? nullptr : A.re + mm * A.ldre + 4 * q;
+    f32x4 xr = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if constexpr (!EW) xr = *reinterpret_cast<const f32x4 *>(rer);  // stage C's first input group
     {
         const int fbase = 16 * half * TPWB + 4 * q;
 #pragma unroll
@@ -457,7 +539,7 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
 
     TC_STAMP(3);
     // ------------------------------------------------------------------ stage C: folded score head
-    f32x4 accC[TPWC];
+    if constexpr (!EW) {
 #pragma unroll
     for (int c = 0; c < TPWC; ++c) accC[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
@@ -472,6 +554,7 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
         buf ^= 1;
     }
     TC_STAMP(4);
+    }
 #pragma unroll
     for (int kg = 0; kg < NTB; ++kg) {  // r_p, straight from LDS (its padding tile, all zeros, is no k-group worth running)
         WT *lw = reinterpret_cast<WT *>(lds) + buf * S::SLAB;
@@ -507,10 +590,10 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     TC_STAMPS_OUT(0);
 }
 
-template <int NTA, int NTB, int NTC, int WM = 0, bool ROWS = false>
+template <int NTA, int NTB, int NTC, int WM = 0, bool ROWS = false, bool EW = false>
 int tc_launch(const TailArgs &a, hipStream_t s) {
     constexpr size_t lds = TcShape<NTA, NTB, NTC>::BYTES;
-    auto kern = tail_chain_kernel<NTA, NTB, NTC, WM, ROWS>;
+    auto kern = tail_chain_kernel<NTA, NTB, NTC, WM, ROWS, EW>;
     LPF_SET_MAX_LDS(kern, lds);  // (per instantiation and device; the attribute is sticky)
     const int64_t blocks = (a.M + 16 * TC_GROUPS - 1) / (16 * TC_GROUPS);
     if (blocks > 0x7fffffff) return LPF_ERR_UNSUPPORTED;
@@ -683,4 +766,35 @@ extern "C" int lpf_tail_chain_rows_perm_bf16(int64_t M, int32_t D, int32_t n_cou
     LPF_REQUIRE(perm && n_full && bC_empty);
     return tc_rows<1>(M, D, n_counts, rows, ldrows, wB_packed_bf16, bB, lnB_g, lnB_b, r_e, ldre, wC_packed_bf16, bC, w_dot,
                          b_dot, sel_ctl, logit, prob, stream, perm, n_full, bC_empty, row_empty);
+}
+
+/* lpf_tail_chain_rows_perm_f32 with stage E in front (the header has the contract): r_e is computed by the tail's own
+ * workgroups from the node table instead of being read. */
+extern "C" int lpf_tail_chain_rows_perm_ew_f32(int64_t M, int32_t D, int32_t n_counts, const float *rows, int64_t ldrows,
+                                               const float *wB_packed, const float *bB, const float *lnB_g,
+                                               const float *lnB_b, const float *r_e, int64_t ldre, const float *wC_packed,
+                                               const float *bC, const float *w_dot, const float *b_dot,
+                                               const int64_t *sel_ctl, const int32_t *perm, const int64_t *n_full,
+                                               const float *bC_empty, const float *row_empty, const float *X, int64_t ldx,
+                                               const int64_t *batch, int64_t batch_ld, int64_t n_rows,
+                                               const float *wE_packed, const float *bE, const float *lnE_g,
+                                               const float *lnE_b, float *logit, float *prob, void *stream) {
+    if (!wE_packed)
+        return lpf_tail_chain_rows_perm_f32(M, D, n_counts, rows, ldrows, wB_packed, bB, lnB_g, lnB_b, r_e, ldre, wC_packed, bC,
+                                            w_dot, b_dot, sel_ctl, perm, n_full, bC_empty, row_empty, logit, prob, stream);
+    if (M == 0) return LPF_OK;
+    if (D != 128) return LPF_ERR_UNSUPPORTED;
+    LPF_REQUIRE(perm && n_full && bC_empty && lpf_aligned16(bC_empty) && (!row_empty || lpf_aligned16(row_empty)));
+    LPF_REQUIRE(M > 0 && rows && wB_packed && bB && lnB_g && lnB_b && wC_packed && bC && w_dot && b_dot && (logit || prob));
+    LPF_REQUIRE((n_counts == 1 || n_counts == 3 || n_counts == 4) && (ldrows & 3) == 0 && ldrows >= D + 4);
+    LPF_REQUIRE(X && batch && bE && lnE_g && lnE_b && n_rows > 0 && batch_ld >= M && (ldx & 3) == 0 && ldx >= D);
+    LPF_REQUIRE(lpf_aligned16(rows) && lpf_aligned16(wB_packed) && lpf_aligned16(wC_packed) && lpf_aligned16(bB) &&
+                lpf_aligned16(lnB_g) && lpf_aligned16(lnB_b) && lpf_aligned16(bC) && lpf_aligned16(w_dot) &&
+                lpf_aligned16(X) && lpf_aligned16(wE_packed) && lpf_aligned16(bE) && lpf_aligned16(lnE_g) &&
+                lpf_aligned16(lnE_b));
+    TailArgs a{M, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, D, nullptr, 0, wB_packed, bB,
+               lnB_g, lnB_b, D + n_counts, nullptr, 0, wC_packed, bC, 2 * D, w_dot, b_dot, logit, prob,
+               nullptr, nullptr, 0, nullptr, nullptr, sel_ctl, n_counts, rows, ldrows, perm, n_full, bC_empty, row_empty,
+               X, ldx, batch, batch_ld, n_rows, wE_packed, bE, lnE_g, lnE_b};
+    return tc_launch<8, 9, 16, 0, true, true>(a, static_cast<hipStream_t>(stream));
 }

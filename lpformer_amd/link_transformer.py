@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import functools
 import math
+import os
 import weakref
 from typing import Optional
 
@@ -623,6 +624,16 @@ class LinkTransformer(nn.Module):
         # behind the pair-major kernel: hand the dense tail the pairs with selected nodes first and let the workgroups that
         # see only pairs without any (their attention branch is a constant) run the elementwise half of the head alone
         self.tail_skip_empty = True
+        # the step of the fp32, D = 128 hot path (query table, select4, pair-major rows with an order) in THREE launches:
+        # lpf_select4_q gathers the query for the pairs that kept an entry, lpf_tail_chain_rows_perm_ew_f32 computes the
+        # elementwise branch's hidden layer itself -- no launch of the elementwise branch, no r_e and no query row of a
+        # pair without entries through memory.  "auto": where those kernels apply AND the step runs on one stream
+        # (``use_side_stream`` off, as under a rotation over several streams) -- with the side stream on, the step stays
+        # the one with the elementwise branch on it, which is what that configuration's tests describe (DESIGN.md 5.1:
+        # not because it is faster); True: wherever the kernels apply; False: four launches everywhere.  Same scores,
+        # bit for bit.
+        # LPF_STEP_FORM=four in the environment (read here, once) is the A/B aid for False.
+        self.fuse_step = False if os.environ.get("LPF_STEP_FORM") == "four" else "auto"
         # "f32" (parity mode, logits within 1e-4 of the reference) or "bf16" (throughput mode of score_pairs: the node
         # table Z is stored in bf16 and Wfold h runs on the bf16 matrix cores; selection and everything else as in f32)
         self.precision = "f32"
@@ -1239,21 +1250,24 @@ class LinkTransformer(nn.Module):
         lo, hi = self.S4_SHAPE_SLOTS
         return 512 if (nblk >= 2 * n_cu and lo <= slots / max(nblk, 1) <= hi) else 0
 
-    def _select4_launch(self, ws, batch, wi, regions: bool = False):
+    def _select4_launch(self, ws, batch, wi, regions: bool = False, q=None):
         """``lpf_select4`` into ``ws`` (a ``_Select4Workspace``, or -- ``regions`` -- the pair-major half of a
-        ``_Select4RegionsWorkspace``)."""
+        ``_Select4RegionsWorkspace``).  ``q = (Y, out)``: ``lpf_select4_q``, which also leaves ``out[p] = Y[a] + Y[b]`` for
+        the pairs that kept an entry."""
         lib, st = _lib.hip(), raw_stream(self.device)
         cn = 1 if self.mask == "cn" else 0
+        name = "lpf_select4" if q is None else "lpf_select4_q"
+        extra = () if q is None else (ptr(q[0]), q[0].stride(0), ptr(q[1]), q[1].stride(0), q[1].shape[1])
         with KernelTimer.span("select_run"):
-            check(lib.lpf_select4(batch.shape[1], ptr(batch), batch.stride(0), self.num_nodes, ptr(wi.rec), ptr(wi.adj_cv),
-                                  ptr(wi.a1_cv), ptr(wi.px_cv), ptr(wi.t0_cv), ptr(wi.u.cv), ptr(wi.mini), cn,
-                                  1 if wi.use_px else 0, float(self.thresh_cn), float(self.thresh_1hop),
-                                  float(self.thresh_non1hop), ptr(ws.ctl), ptr(ws.pair_tab), ptr(ws.blk_cnt),
-                                  ptr(getattr(ws, "blk_types", None)), ptr(ws.entries4 if regions else ws.entries),
-                                  ws.ent_cap4 if regions else ws.ent_cap,
-                                  self.select4_threads or getattr(ws, "shape", 0), st), "lpf_select4")
+            check(getattr(lib, name)(batch.shape[1], ptr(batch), batch.stride(0), self.num_nodes, ptr(wi.rec), ptr(wi.adj_cv),
+                                     ptr(wi.a1_cv), ptr(wi.px_cv), ptr(wi.t0_cv), ptr(wi.u.cv), ptr(wi.mini), cn,
+                                     1 if wi.use_px else 0, float(self.thresh_cn), float(self.thresh_1hop),
+                                     float(self.thresh_non1hop), ptr(ws.ctl), ptr(ws.pair_tab), ptr(ws.blk_cnt),
+                                     ptr(getattr(ws, "blk_types", None)), ptr(ws.entries4 if regions else ws.entries),
+                                     ws.ent_cap4 if regions else ws.ent_cap,
+                                     self.select4_threads or getattr(ws, "shape", 0), *extra, st), name)
 
-    def _select4_device(self, batch: torch.Tensor, test_set: bool) -> "_Select4Workspace":
+    def _select4_device(self, batch: torch.Tensor, test_set: bool, q=None) -> "_Select4Workspace":
         """The one-launch selection for the hot path (``lpf_select4``): pair-major entries, a table entry per pair,
         nothing read back.  The entry buffer is sized from earlier batches (a batch needs room for its candidate
         slots, which the kernel reports in ``ctl[0]``); a batch that does not fit raises the sticky error bits, its
@@ -1280,7 +1294,7 @@ class LinkTransformer(nn.Module):
             self._select4_launch(ws, batch, wi)
             ws.kept_cap = 2 * ws.kept() + 65536
             ws.calibrated = True
-        self._select4_launch(ws, batch, wi)
+        self._select4_launch(ws, batch, wi, q=q)
         return ws
 
     def check_selection(self, stream=None) -> bool:
@@ -1696,20 +1710,28 @@ class LinkTransformer(nn.Module):
         """True when the one-pass attention runs pair-major and hands over finished rows (csrc/pair_rows.hip)."""
         return self.attention_rows and self.attention_kernel() == "flip"
 
-    def _attention_rows(self, batch, x_node, test_set, adj_mask, side, out, n_counts, order=False, q=None):
+    def _attention_rows(self, batch, x_node, test_set, adj_mask, side, out, n_counts, order=False, q=None, q_tab=None):
         """q gather -> selection -> pair-major one-pass attention writing ``out[p] = [post_att_norm(attention output) |
         n_counts count features]`` (``out``: [BS, ld] fp32, ld % 4 == 0).  Returns the selection workspace; with
         ``order`` also (perm int32[BS], n_nonempty int64[1]): the pairs with selected nodes first, for
-        ``lpf_tail_chain_rows_perm_*``."""
+        ``lpf_tail_chain_rows_perm_*``.  ``q_tab`` (the three-launch step, behind select4 only): the query table Y -- the
+        selection's launch gathers the query itself, for the pairs that kept an entry."""
         lib, st, d = _lib.hip(), raw_stream(self.device), self.dim
         bs = batch.shape[1]
         w = self._fold()
         z = self._node_keys(x_node, w)
+        four = self._uses_select4(adj_mask)
+        q_sel = None
+        if q_tab is not None:
+            assert four and q is None and side is None
+            # (per stream, like every workspace.  Only the rows of pairs with entries are written -- and only those are
+            #  read: the attention kernel fetches a query for pairs of entries, csrc/pair_rows.hip q_row)
+            q = self._workspace("att_q", bs * d, torch.float32, st)[:bs * d].view(bs, d)
+            q_sel = (q_tab, q)
         if q is None:   # (score_pairs has it gathered by the elementwise branch's launch)
             with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(self.device)):
                 q = self._pair_q(batch, x_node, w)
-        four = self._uses_select4(adj_mask)
-        ws = self._select4_device(batch, test_set) if four else self._select_device(batch, test_set, adj_mask)
+        ws = self._select4_device(batch, test_set, q=q_sel) if four else self._select_device(batch, test_set, adj_mask)
         if side is not None:
             _lib.stream_wait(torch.cuda.current_stream(self.device), side)
         layer = self.att_layers[0]
@@ -1959,6 +1981,46 @@ class LinkTransformer(nn.Module):
         finally:
             self._fold_memo = None
 
+    def _three_launches(self, x_node, adj_mask) -> bool:
+        """The one decision of a ``score_pairs`` call between the three-launch step and everything as it was
+        (``fuse_step``): fp32, D = 128, the query from its table, select4, pair-major rows with an order -- and, for
+        "auto", a step without the side stream."""
+        ew = self.elementwise_lin
+        if self.fuse_step == "auto" and self.use_side_stream:
+            return False
+        return bool(self.fuse_step and self.dim == 128 and self.precision == "f32" and self.tail_precision == "f32" and
+                    self.query_from == "table" and self.tail_skip_empty and ew.norm is not None and
+                    tuple(ew.linears[0].weight.shape) == (128, 128) and x_node.shape[1] == 128 and
+                    x_node.stride(0) % 4 == 0 and x_node.data_ptr() % 16 == 0 and
+                    self._uses_rows() and self._uses_select4(adj_mask))
+
+    def _score_pairs_three(self, batch, x_node, score_func, test_set, a, c, logits):
+        """``lpf_select4_q`` -> ``lpf_pair_attention_rows4_f32`` -> ``lpf_tail_chain_rows_perm_ew_f32`` on the current
+        stream: no buffer for r_e, no side stream.  None when the library has no such tail for this shape (the caller
+        then takes the four-launch path; nothing this call queued is used)."""
+        lib, st, d = _lib.hip(), raw_stream(self.device), self.dim
+        bs = batch.shape[1]
+        ew = self.elementwise_lin
+        self._prepare_pair_major(None)
+        y = self._node_y(x_node, self._fold())
+        te = ew._chain1.tables(ew.linears[0].weight, ew.linears[0].bias, ew.norm.weight, ew.norm.bias)
+        rows = self._zero_workspace("att_rows", bs * (d + 4), st).view(bs, d + 4)   # (pad columns stay zero)
+        ws, perm, nfull = self._attention_rows(batch, x_node, test_set, None, None, rows, self.count_dim, order=True,
+                                               q_tab=y)
+        tt = self._tail_tables(score_func, a, c)
+        res = torch.empty(bs, dtype=torch.float32, device=self.device)
+        with KernelTimer.span("tail_chain"):
+            rc = lib.lpf_tail_chain_rows_perm_ew_f32(
+                bs, d, self.count_dim, ptr(rows), rows.stride(0), ptr(tt["wB"]), ptr(tt["bB"]), ptr(tt["lnB_g"]),
+                ptr(tt["lnB_b"]), None, 0, ptr(tt["wC"]), ptr(tt["bC"]), ptr(tt["w_dot"]), ptr(tt["b_dot"]), ptr(ws.ctl),
+                ptr(perm), ptr(nfull), ptr(tt["bC_empty"]), ptr(tt["row_empty"]), ptr(x_node), x_node.stride(0),
+                ptr(batch), batch.stride(0), x_node.shape[0], ptr(te["w1p"]), ptr(te["b1"]), ptr(te["ln_g"]),
+                ptr(te["ln_b"]), ptr(res) if logits else None, None if logits else ptr(res), st)
+        if rc == _lib.CONST["LPF_ERR_UNSUPPORTED"]:
+            return None
+        check(rc, "lpf_tail_chain_rows_perm_ew_f32")
+        return res
+
     def _score_pairs_folded(self, batch, X_node, score_func, test_set, adj_mask, logits):
         with torch.no_grad():
             d, pd = self.dim, self.dim + self.count_dim
@@ -1966,9 +2028,13 @@ class LinkTransformer(nn.Module):
             bs = batch.shape[1]
             x_node = f32_rows(X_node)
             a, c, kpad = self._score_fold(score_func)
-            r = torch.empty(bs, kpad, dtype=torch.float32, device=self.device)  # [r_e | r_p | pad]
             ew, pw = self.elementwise_lin, self.pairwise_lin
             one_pass = d in (32, 64, 128, 256) and self.use_tail_chain and self.use_fused_attention and bs > 0
+            if one_pass and self._three_launches(x_node, adj_mask):
+                res = self._score_pairs_three(batch, x_node, score_func, test_set, a, c, logits)
+                if res is not None:
+                    return res
+            r = torch.empty(bs, kpad, dtype=torch.float32, device=self.device)  # [r_e | r_p | pad]
             # the attention's query q = Y[a] + Y[b] is gathered by the launch of the elementwise branch (same ids, a
             # second table): one launch less per step -- 19 us of a 193 us pipelined step as a launch of its own
             q_side = None

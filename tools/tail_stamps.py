@@ -1,5 +1,7 @@
 """Tuning aid: phase marks of tail_chain_kernel (build with EXTRA=-DTC_STAMPS): per wavefront start / stage A read /
-stage B k-groups done / LayerNorm B done / stage C r_e k-groups done / r_p k-groups done / end."""
+stage B k-groups done / LayerNorm B done / stage C r_e k-groups done / r_p k-groups done / end; in the three-launch step
+(model.fuse_step, the default at D = 128 fp32) also stage E done, and the r_e k-groups then come BEFORE the rows read.
+16 words per wavefront: marks 0-7, word 15 = the kind (0 full workgroup, 1 pairs without selected nodes)."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -20,7 +22,7 @@ h = model.propagate()
 lib = _lib.hip()
 fn = lib.lpf_tail_chain_set_stamps
 fn.argtypes = [ctypes.c_void_p]; fn.restype = ctypes.c_int
-buf = torch.zeros(2048 * 8 * 8, dtype=torch.int64, device=dev)
+buf = torch.zeros(2048 * 8 * 16, dtype=torch.int64, device=dev)
 for b in batches * 3:
     model.score_pairs(b, h, score)
 torch.cuda.synchronize()
@@ -30,20 +32,24 @@ for i, b in enumerate(batches[:2]):
     buf.zero_()
     model.score_pairs(b, h, score)
     torch.cuda.synchronize()
-    v = buf.view(-1, 8).cpu().numpy().astype(np.float64)
+    v = buf.view(-1, 16).cpu().numpy().astype(np.float64)
     v = v[v[:, 0] > 0]
     t0 = v[:, 0].min()
+    ew = bool((v[:, 7] > 0).any())     # stage E form: start, E, C: r_e, rows read, stage B, LN B, C: r_p, end
+    order = [0, 7, 4, 1, 2, 3, 5, 6] if ew else list(range(7))
+    names = ["start", "rows read", "stage B loop", "LN B", "C: r_e loop", "C: r_p loop", "end", "stage E"]
     for kind, tag in ((0, "full workgroups"), (1, "workgroups of pairs without selected nodes")):
-        s = v[v[:, 7] == kind]
+        s = v[v[:, 15] == kind]
         if not len(s):
             continue
-        rel = (s[:, :7] - t0) / 100.0
+        rel = (s[:, :8] - t0) / 100.0
         print(f"batch {i}, {tag}: {len(s)} wavefronts; last end {rel[:, 6].max():.1f} us")
-        for k in range(7):
-            if kind == 1 and 0 < k < 6:
+        for k in order:
+            if kind == 1 and k not in ((0, 7, 4, 6) if ew else (0, 6)):
                 continue
             print(f"   {names[k]:14s} p10 {np.percentile(rel[:, k], 10):6.1f}  p50 {np.percentile(rel[:, k], 50):6.1f}  "
                   f"p90 {np.percentile(rel[:, k], 90):6.1f}  max {rel[:, k].max():6.1f}")
         if kind == 0:
-            d = np.diff(rel, axis=1)
-            print("   phase lengths, median:", " ".join(f"{names[k + 1]} {np.median(d[:, k]):.1f}" for k in range(6)))
+            d = np.diff(rel[:, order], axis=1)
+            print("   phase lengths, median:", " ".join(f"{names[order[k + 1]]} {np.median(d[:, k]):.1f}"
+                                                        for k in range(len(order) - 1)))
