@@ -7,7 +7,8 @@
 // Same machinery as dense_chain.hip (samples on the MFMA columns, a pair of wavefronts per 16 samples splitting the
 // feature tiles, weights host-packed in A-operand order and staged global -> registers -> LDS one k-group ahead,
 // double-buffered, one barrier per stage), with three stages chained through LDS: a stage's accumulators, written in
-// accumulator layout, are the next stage's B operands.  Stage B appends one k-group read from global memory (the
+// accumulator layout, are the next stage's B operands.  What the stage boundaries read besides -- biases, LayerNorm
+// weights, w_dot -- is requested once at the start of the workgroup and waits in LDS.  Stage B appends one k-group read from global memory (the
 // count features), stage C starts with k-groups read from global memory (r_e, produced on the side stream by the
 // elementwise branch).  Against three separate launches this removes two launch ramps and the round trips of the
 // attention output and of r_p through HBM.
@@ -102,6 +103,15 @@ __device__ __forceinline__ void tc_store(const T (&r)[P], T *slab, int tid) {
     for (int e = 0; e < P; ++e) slab[e * TC_THREADS + tid] = r[e];
 }
 
+// The k-loops mean "barrier, request k-group kg + 1, MFMAs of kg".  In the unrolled loops of stage E and of stage C over
+// r_p the scheduler, left alone, sinks the request to the end of the k-group -- directly in front of its own wait, the
+// store and the next barrier, one exposed L2 round trip per k-group -- and pulls the next store and barrier into the
+// MFMA stream.  Nothing is scheduled across a TC_PIN(): one behind the request keeps it in front of the MFMAs, one at
+// the end of the k-group keeps the wait behind them.  The rolled loops and stage B keep the order by themselves
+// (tools/tail_isa.py counts the MFMAs between every request and its wait, per instantiation); pinned as well they
+// measured slower (EXPERIMENTS.md), so they are left to the scheduler.
+#define TC_PIN() __builtin_amdgcn_sched_barrier(0)
+
 // acc[c] += W[16 (c0 + c) + i][k-group] * bv for this wave's TPW tiles; lw = slab + c0 * 64 + lane.  last = false (the
 // same for the whole wavefront): the wave's last tile is padding -- all-zero weight rows -- and is left out.
 template <int TPW>
@@ -133,7 +143,12 @@ __device__ __forceinline__ void tc_mfma(f32x4 (&acc)[TPW], const uint2 *lw, cons
     }
 }
 
-// LayerNorm over the n real features held by the wave pair (this wave: TPW tiles from feature fbase), in place
+// LayerNorm over the n real features held by the wave pair (this wave: TPW tiles from feature fbase), in place.
+// my_x / peer_x: this wave's and its peer's word of the exchange slot of s1; those of s2 lie TC_XCH_SLOT floats behind.
+// Every exchange of the kernel has a slot of its own (TcShape) and a workgroup runs the kernel's stages once, so a slot
+// is written once in a workgroup's life: there is no earlier value somebody could still be reading, and the only barrier
+// an exchange needs is the one between its write and its read.
+constexpr int TC_XCH_SLOT = TC_WAVES * 16;
 template <int TPW>
 __device__ __forceinline__ void tc_layernorm(f32x4 (&acc)[TPW], int fbase, int n, const float *g, const float *b, int half,
                                              int q, float *my_x, const float *peer_x, bool relu) {
@@ -141,7 +156,6 @@ __device__ __forceinline__ void tc_layernorm(f32x4 (&acc)[TPW], int fbase, int n
 #pragma unroll
     for (int c = 0; c < TPW; ++c) s1 += acc[c][0] + acc[c][1] + acc[c][2] + acc[c][3];
     s1 = lpf_quad_sum(s1);  // padded features are exactly 0 and add nothing
-    __syncthreads();       // exchange slots free
     if (q == 0) *my_x = s1;
     __syncthreads();
     const float mean = (half == 0 ? s1 + *peer_x : *peer_x + s1) / (float)n;  // same order in both waves
@@ -154,10 +168,10 @@ __device__ __forceinline__ void tc_layernorm(f32x4 (&acc)[TPW], int fbase, int n
             s2 += d * d;
         }
     s2 = lpf_quad_sum(s2);
+    if (q == 0) my_x[TC_XCH_SLOT] = s2;
     __syncthreads();
-    if (q == 0) *my_x = s2;
-    __syncthreads();
-    const float rstd = 1.0f / sqrtf((half == 0 ? s2 + *peer_x : *peer_x + s2) / (float)n + 1e-5f);
+    const float p2 = peer_x[TC_XCH_SLOT];
+    const float rstd = 1.0f / sqrtf((half == 0 ? s2 + p2 : p2 + s2) / (float)n + 1e-5f);
 #pragma unroll
     for (int c = 0; c < TPW; ++c) {
         const f32x4 gg = *reinterpret_cast<const f32x4 *>(g + fbase + 16 * c);  // zero-padded: pads come out 0
@@ -192,7 +206,13 @@ struct TcShape {
     static constexpr int SLAB = PM * TC_THREADS;
     static constexpr int HT = NTPA > NTPB ? NTPA : NTPB;  // hidden tiles kept per sample group
     static constexpr int HID = TC_GROUPS * HT * 64;
-    static constexpr size_t BYTES = (size_t)(2 * SLAB + HID) * sizeof(f32x4) + TC_WAVES * 16 * sizeof(float);
+    // exchange slots: s1, s2 of the first LayerNorm (E, or A in the forms that have one), s1, s2 of LayerNorm B, the score dot
+    static constexpr int XCH = 5 * TC_WAVES * 16;
+    // the boundary vectors, staged in LDS once per workgroup (floats): bE, lnE_g, lnE_b | bB, lnB_g, lnB_b | bC (or
+    // bC_empty), w_dot -- each zero-padded by the host to its stage's padded tiles
+    static constexpr int VEC_B = 3 * 16 * NTPA, VEC_C = VEC_B + 3 * 16 * NTPB, VEC_N = VEC_C + 2 * 16 * NTPC;
+    static constexpr size_t BYTES = (size_t)(2 * SLAB + HID) * sizeof(f32x4) + (XCH + VEC_N) * sizeof(float);
+    static_assert(NTC >= 32 || BYTES <= 81920, "two workgroups share a CU's 160 KB of LDS");
 };
 
 // (D = 256: 32 output tiles of the score head -- 16 accumulators per lane in stage C alone --, one workgroup per CU with
@@ -213,8 +233,9 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     float *xch = reinterpret_cast<float *>(hid + S::HID);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int grp = wave >> 1, half = wave & 1, q = lane >> 4, j = lane & 15;
-    float *my_x = xch + wave * 16 + j;
+    float *my_x = xch + wave * 16 + j;                  // (slot 0; slot k lies k * TC_XCH_SLOT floats behind)
     const float *peer_x = xch + (wave ^ 1) * 16 + j;
+    float *vec = xch + S::XCH;
     f32x4 *my_hid = hid + (grp * S::HT) * 64 + lane;
     int buf = 0;
 #ifdef TC_STAMPS
@@ -240,6 +261,62 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     bool no_sel = false;        // (rows mode with an order: this pair has no selected nodes)
     if constexpr (ROWS) no_sel = A.perm && A.row_empty && (live ? pos : A.M - 1) >= *A.n_full;
 
+    // The boundary vectors (about 1.4 k floats at D = 128) go through LDS: requested here, one 16-byte piece per thread,
+    // written (tc_vec_publish) in front of the first barrier of whichever path the workgroup takes -- by then the wait
+    // for the first weight stage, requested behind them, has covered them -- and read where the LayerNorms and the
+    // epilogue used to wait for a global round trip each.  Threads past the last piece request and write the last piece
+    // again (the same value to the same place): with a guard around the write the request is sunk into the guard, to
+    // the far end of everything requested in between.
+    constexpr int VP0 = EW ? 0 : S::VEC_B / 4, VPN = S::VEC_N / 4 - VP0, VPT = (VPN + TC_THREADS - 1) / TC_THREADS;
+    f32x4 vecr[VPT];
+#pragma unroll
+    for (int e = 0; e < VPT; ++e) {
+        int p = VP0 + e * TC_THREADS + tid;
+        p = p < S::VEC_N / 4 ? p : S::VEC_N / 4 - 1;
+        const float *src;
+        if (p >= S::VEC_C / 4) {
+            const int o = p - S::VEC_C / 4;
+            src = o < 4 * NTPC ? (lite ? A.bC_empty : A.bC) + 4 * o : A.wdot + 4 * (o - 4 * NTPC);
+        } else if (!EW || p >= S::VEC_B / 4) {
+            const int o = p - S::VEC_B / 4;
+            src = o < 4 * NTPB ? A.bB + 4 * o : (o < 8 * NTPB ? A.lnB_g + 4 * (o - 4 * NTPB) : A.lnB_b + 4 * (o - 8 * NTPB));
+        } else {
+            src = p < 4 * NTPA ? A.bE + 4 * p : (p < 8 * NTPA ? A.lnE_g + 4 * (p - 4 * NTPA) : A.lnE_b + 4 * (p - 8 * NTPA));
+        }
+        vecr[e] = *reinterpret_cast<const f32x4 *>(src);
+    }
+    TC_PIN();   // (the requests stay here, in front of whatever the first stage gathers)
+    auto tc_vec_publish = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int e = 0; e < VPT; ++e) {
+            int p = VP0 + e * TC_THREADS + tid;
+            p = p < S::VEC_N / 4 ? p : S::VEC_N / 4 - 1;
+            reinterpret_cast<f32x4 *>(vec)[p] = vecr[e];
+        }
+    };
+    const float *v_bE = vec, *v_lnE_g = vec + 16 * NTPA, *v_lnE_b = vec + 32 * NTPA;
+    const float *v_bB = vec + S::VEC_B, *v_lnB_g = v_bB + 16 * NTPB, *v_lnB_b = v_bB + 32 * NTPB;
+    const float *v_bC = vec + S::VEC_C, *v_wdot = v_bC + 16 * NTPC;
+
+    // rows mode: a pair's finished row and its count features, all pieces requested together -- addresses clamped into
+    // the row, the values selected where stage A and stage B take them.  The counts are read from the
+    // pair's own row even where the pair takes the constant row: row_empty has no counts, and the value is dropped.
+    f32x4 rowv[ROWS ? TPWA : 1], rowt = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < (ROWS ? TPWA : 1); ++c) rowv[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    auto tc_rows_request = [&]() __attribute__((always_inline)) {
+        if constexpr (ROWS) {
+            const int fbase = 16 * half * TPWA + 4 * q;
+            const float *own = A.rows + mm * A.ldrows, *row = no_sel ? A.row_empty : own;
+#pragma unroll
+            for (int c = 0; c < TPWA; ++c) {
+                const int f0 = fbase + 16 * c;
+                rowv[c] = *reinterpret_cast<const f32x4 *>(row + (f0 < A.NA ? f0 : 0));
+            }
+            rowt = *reinterpret_cast<const f32x4 *>(own + A.NA);
+        }
+    };
+
     f32x4 accC[TPWC];           // stage C's accumulators (with stage E they are filled first and live across A and B)
     if constexpr (EW) {
         static_assert(ROWS && WM == 0 && S::PA == 1 && NTPA == NTA && NGE % 2 == 0 && 2 * tc_stage_stride(NTPA) <= S::SLAB &&
@@ -249,6 +326,9 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
         // sixteen 16-byte pieces of the two rows are requested at once, in front of the first k-group (the kernel's
         // other stages need the registers only later), so the gather is one round trip, not one per k-group
         int64_t ra = A.batch[mm], rb = A.batch[A.batch_ld + mm];
+        WT wrE[2];
+        tc_load<2, 2 * NTPA>(wrE, A.wE, 0, tid);
+        TC_PIN();   // (the first weights are requested next to the ids, not behind the sixteen pieces of the rows)
         if ((uint64_t)ra >= (uint64_t)A.n_rows) ra = 0;
         if ((uint64_t)rb >= (uint64_t)A.n_rows) rb = 0;
         const float *xa = A.X + ra * A.ldX + 4 * q, *xb = A.X + rb * A.ldX + 4 * q;
@@ -257,14 +337,13 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
         for (int c = 0; c < TPWA; ++c) accE[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
         // (two k-groups per weight stage and barrier: a k-group of this layer is 512 float4, a slab holds 1,024; the
         //  k-groups still reach an accumulator in ascending order)
-        WT wrE[2];
-        tc_load<2, 2 * NTPA>(wrE, A.wE, 0, tid);
         f32x4 xra[NGE], xrb[NGE];
 #pragma unroll
         for (int kg = 0; kg < NGE; ++kg) {
             xra[kg] = *reinterpret_cast<const f32x4 *>(xa + 16 * kg);
             xrb[kg] = *reinterpret_cast<const f32x4 *>(xb + 16 * kg);
         }
+        tc_vec_publish();
 #pragma unroll
         for (int kg = 0; kg < NGE; kg += 2) {
             const f32x4 bv0 = xra[kg] * xrb[kg], bv1 = xra[kg + 1] * xrb[kg + 1];
@@ -272,17 +351,22 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
             tc_store<2>(wrE, lw, tid);
             __syncthreads();
             if (kg + 2 < NGE) tc_load<2, 2 * NTPA>(wrE, A.wE, kg / 2 + 1, tid);
+            TC_PIN();
             tc_mfma<TPWA>(accE, lw + (half * TPWA) * 64 + lane, bv0);
             tc_mfma<TPWA>(accE, lw + tc_stage_stride(NTPA) + (half * TPWA) * 64 + lane, bv1);
+            TC_PIN();
             buf ^= 1;
         }
+        // stage A's rows: requested here, a LayerNorm and eight k-groups ahead of their use (the registers of the gathered
+        // rows are free from here on), instead of one more round trip in front of stage B
+        if (!lite) tc_rows_request();
         WT wrCe[S::PC];
         tc_load<S::PC, NTPC>(wrCe, A.wC, 0, tid);  // stage C's first weights fly during the epilogue
         {   // bias -> LayerNorm -> ReLU: dense_chain.hip's epilogue 1, same operations in the same order
             const int fbase = 16 * half * TPWA + 4 * q;
 #pragma unroll
-            for (int c = 0; c < TPWA; ++c) accE[c] += *reinterpret_cast<const f32x4 *>(A.bE + fbase + 16 * c);
-            tc_layernorm<TPWA>(accE, fbase, A.NA, A.lnE_g, A.lnE_b, half, q, my_x, peer_x, true);
+            for (int c = 0; c < TPWA; ++c) accE[c] += *reinterpret_cast<const f32x4 *>(v_bE + fbase + 16 * c);
+            tc_layernorm<TPWA>(accE, fbase, A.NA, v_lnE_g, v_lnE_b, half, q, my_x, peer_x, true);
 #pragma unroll
             for (int c = 0; c < TPWA; ++c) my_hid[(half * TPWA + c) * 64] = accE[c];
         }
@@ -315,6 +399,7 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
             const float *rer = A.re + mm * A.ldre + 4 * q;
             tc_load<S::PC, NTPC>(wr, A.wC, 0, tid);
             f32x4 xr = *reinterpret_cast<const f32x4 *>(rer);
+            tc_vec_publish();
 #pragma unroll 1
             for (int kg = 0; kg < NGE; ++kg) {
                 const f32x4 bv = xr;
@@ -333,16 +418,16 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
             float d = 0.f;
 #pragma unroll
             for (int c = 0; c < TPWC; ++c) {
-                const f32x4 b = *reinterpret_cast<const f32x4 *>(A.bC_empty + fbase + 16 * c);
-                const f32x4 w = *reinterpret_cast<const f32x4 *>(A.wdot + fbase + 16 * c);
+                const f32x4 b = *reinterpret_cast<const f32x4 *>(v_bC + fbase + 16 * c);   // (bC_empty: lite)
+                const f32x4 w = *reinterpret_cast<const f32x4 *>(v_wdot + fbase + 16 * c);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) d = fmaf(fmaxf(acc[c][r] + b[r], 0.f), w[r], d);
             }
             d = lpf_quad_sum(d);
-            if (q == 0) *my_x = d;
+            if (q == 0) my_x[4 * TC_XCH_SLOT] = d;
             __syncthreads();
             if (live && q == 0 && half == 0) {
-                d = d + *peer_x + A.bdot[0];
+                d = d + peer_x[4 * TC_XCH_SLOT] + A.bdot[0];
                 if (A.sel_ctl && A.sel_ctl[3] != 0) d = __builtin_nanf("");
                 if (A.logit) A.logit[m] = d;
                 if (A.prob) A.prob[m] = 1.0f / (1.0f + expf(-d));
@@ -352,6 +437,7 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
             return;
         }
     }
+    if constexpr (!EW) tc_vec_publish();   // (in front of this path's first barrier: stage A's, or stage B's first k-group)
     // ------------------------------------------------------------------ stage A: attention output + post-norm
     f32x4 accA[TPWA];
 #pragma unroll
@@ -384,13 +470,9 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     tc_load<S::PB, NTPB>(wrB, A.wB, 0, tid);  // stage B's first weights fly during the epilogue
     if constexpr (ROWS) {
         const int fbase = 16 * half * TPWA + 4 * q;
-        const float *row = no_sel ? A.row_empty : A.rows + mm * A.ldrows;
+        if constexpr (!EW) tc_rows_request();
 #pragma unroll
-        for (int c = 0; c < TPWA; ++c) {
-            const int f0 = fbase + 16 * c;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(row + (f0 < A.NA ? f0 : 0));
-            accA[c] = f0 < A.NA ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
+        for (int c = 0; c < TPWA; ++c) accA[c] = fbase + 16 * c < A.NA ? rowv[c] : (f32x4){0.f, 0.f, 0.f, 0.f};
     } else if (A.part == nullptr) {
         const int fbase = 16 * half * TPWA + 4 * q;
         f32x4 ad[TPWA];
@@ -498,10 +580,10 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     {
         // the appended k-group: the count features (4 floats per sample) in lane quarter 0, zeros elsewhere
         f32x4 tailv = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (q == 0) {
-            if constexpr (ROWS) {
-                if (!no_sel) tailv = *reinterpret_cast<const f32x4 *>(A.rows + mm * A.ldrows + A.NA);
-            } else if (A.part == nullptr) {
+        if constexpr (ROWS) {
+            if (q == 0 && !no_sel) tailv = rowt;
+        } else if (q == 0) {
+            if (A.part == nullptr) {
                 tailv = *reinterpret_cast<const f32x4 *>(A.tail + mm * A.ldtail);
             } else {  // get_structure_cnts (link_transformer.py:340-356): n_cn, n_1hop, [n_non1hop,] n_cn + n_1hop
                 const float n0 = (float)seg_cnt[0], n1 = (float)seg_cnt[1], n2 = (float)seg_cnt[2];
@@ -530,8 +612,8 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     {
         const int fbase = 16 * half * TPWB + 4 * q;
 #pragma unroll
-        for (int c = 0; c < TPWB; ++c) accB[c] += *reinterpret_cast<const f32x4 *>(A.bB + fbase + 16 * c);
-        tc_layernorm<TPWB>(accB, fbase, A.NB, A.lnB_g, A.lnB_b, half, q, my_x, peer_x, true);
+        for (int c = 0; c < TPWB; ++c) accB[c] += *reinterpret_cast<const f32x4 *>(v_bB + fbase + 16 * c);
+        tc_layernorm<TPWB>(accB, fbase, A.NB, v_lnB_g, v_lnB_b, half, q, my_x + 2 * TC_XCH_SLOT, peer_x + 2 * TC_XCH_SLOT, true);
         // (the barriers inside the LayerNorm exchange come after every wave's last read of stage A's tiles)
 #pragma unroll
         for (int c = 0; c < TPWB; ++c) my_hid[(half * TPWB + c) * 64] = accB[c];
@@ -561,7 +643,9 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
         tc_store<S::PC>(wrC, lw, tid);
         __syncthreads();  // (kg == 0: also publishes stage B's hidden tiles)
         if (kg + 1 < NTB) tc_load<S::PC, NTPC>(wrC, A.wC, NGE + kg + 1, tid);
+        TC_PIN();
         tc_mfma<TPWC>(accC, lw + (half * TPWC) * 64 + lane, my_hid[kg * 64]);
+        TC_PIN();
         buf ^= 1;
     }
     TC_STAMP(5);
@@ -570,17 +654,16 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
         float d = 0.f;
 #pragma unroll
         for (int c = 0; c < TPWC; ++c) {
-            const f32x4 b = *reinterpret_cast<const f32x4 *>(A.bC + fbase + 16 * c);
-            const f32x4 w = *reinterpret_cast<const f32x4 *>(A.wdot + fbase + 16 * c);  // zero-padded
+            const f32x4 b = *reinterpret_cast<const f32x4 *>(v_bC + fbase + 16 * c);
+            const f32x4 w = *reinterpret_cast<const f32x4 *>(v_wdot + fbase + 16 * c);  // zero-padded
 #pragma unroll
             for (int r = 0; r < 4; ++r) d = fmaf(fmaxf(accC[c][r] + b[r], 0.f), w[r], d);
         }
         d = lpf_quad_sum(d);
-        __syncthreads();  // exchange slots free (the LayerNorm exchanges have been read by everyone)
-        if (q == 0) *my_x = d;
+        if (q == 0) my_x[4 * TC_XCH_SLOT] = d;
         __syncthreads();
         if (live && q == 0 && half == 0) {
-            d = d + *peer_x + A.bdot[0];
+            d = d + peer_x[4 * TC_XCH_SLOT] + A.bdot[0];
             if (A.sel_ctl && A.sel_ctl[3] != 0) d = __builtin_nanf("");  // the batch did not fit the selection workspace
             if (A.logit) A.logit[m] = d;
             if (A.prob) A.prob[m] = 1.0f / (1.0f + expf(-d));
