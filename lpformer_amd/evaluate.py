@@ -440,27 +440,77 @@ def split_metrics(pos_train, pos_valid, neg_valid, pos_test, neg_test, k_list=(1
     return {key: tuple(part[key] for part in parts) for key in parts[0]}
 
 
+def target_negatives(pos, neg) -> torch.Tensor:
+    """ogbl-citation2's negatives -- K candidate TARGETS per positive, ``neg`` [P, K] -- as the [P, K, 2] pairs
+    (source of positive p, neg[p, k]) that ``test_edge_citation2`` scores (testing.py:21-27).  ``pos`` [P, 2]."""
+    pos, neg = torch.as_tensor(pos), torch.as_tensor(neg)
+    if pos.dim() != 2 or pos.shape[1] != 2 or neg.dim() != 2 or neg.shape[0] != pos.shape[0]:
+        raise ValueError(f"target-only negatives need pos [P, 2] and neg [P, K], got {tuple(pos.shape)} and {tuple(neg.shape)}")
+    return torch.stack((pos[:, :1].to(neg.device).expand_as(neg), neg), dim=-1)
+
+
+def _target_only(data, heart: bool) -> bool:
+    """Whether ``data`` takes the reference's ``test_citation2`` path (train_model.py:114-117: a citation dataset without
+    ``--heart``): its negatives are target ids [P, K], not pairs.  Decided by ``data['dataset']``, as the reference
+    decides by ``args.data_name``; a dict without that key holds [M, 2] shared pairs."""
+    return (not heart) and "citation" in str(data.get("dataset", "")).lower()
+
+
+def _negatives_layout(data, heart: bool) -> str:
+    """``split_metrics``' layout for the negatives of ``data``: "rows" (per positive) or "shared"."""
+    return "rows" if (heart or _target_only(data, heart)) else "shared"
+
+
 @torch.no_grad()
-def evaluate_model(model, score_func, data, batch_size: int = 32768, k_list=(100,), heart: bool = False) -> dict:
-    """The reference's ``test()`` (testing.py:124-161): score ``train_pos_val``, ``valid_pos``, ``test_pos`` and the
-    negatives of ``data`` (one encoder pass per graph; the test split on the test-time graph) and hand the scores,
-    still on the device, to ``split_metrics``.  ``heart``: ``valid_neg`` / ``test_neg`` are [P, K, 2] per-positive
-    negatives (``score_negatives``, the citation2 metrics); otherwise [M, 2] shared ones."""
+def score_splits(model, score_func, data, batch_size: int = 32768, heart: bool = False, logits: bool = False) -> dict:
+    """Scores of the five splits ``test()`` / ``test_citation2()`` score (testing.py:50-74, :124-161), on the device:
+    ``{"train_pos_val", "valid_pos", "test_pos": [P], "valid_neg", "test_neg": [M] shared or [P, K] per positive}``.
+    One encoder pass per graph; ``test_pos`` and ``test_neg`` on the test-time graph (``test_set=True``: encoder,
+    typing adjacency and PPR matrix).  Negatives: [M, 2] shared ones; with ``heart`` [P, K, 2] per positive; for
+    ogbl-citation2 without ``heart`` (``data['dataset']`` names it, as the reference's dispatch does) [P, K] target ids,
+    paired with the source of their positive (``target_negatives``).
+
+    Deliberately NOT the reference where it contradicts itself: ``test_heart_negatives`` encodes with
+    ``model.propagate()`` -- the TRAINING graph -- even for the test negatives (testing.py:105, under a "TODO"), while it
+    types and weighs them on the test graph and scores the test positives entirely on the test graph.  The two differ
+    when ``use_val_in_test`` and ``heart`` are both on; here the test negatives see the same graph as the positives they
+    are ranked against.  The reference's scores are ``score_negatives(..., h=model.propagate(test_set=False),
+    test_set=True)``."""
     model.eval()
     score_func.eval()
+    kw = dict(logits=logits)
     h = model.propagate(test_set=False)
     h_test = model.propagate(test_set=True)
-    pos_train = score_edges(model, score_func, data["train_pos_val"], batch_size, h=h)
-    pos_valid = score_edges(model, score_func, data["valid_pos"], batch_size, h=h)
-    pos_test = score_edges(model, score_func, data["test_pos"], batch_size, h=h_test, test_set=True)
-    if heart:
-        neg_valid = score_negatives(model, score_func, data["valid_neg"], batch_size, h=h)
-        neg_test = score_negatives(model, score_func, data["test_neg"], batch_size, h=h_test, test_set=True)
+    out = {"train_pos_val": score_edges(model, score_func, data["train_pos_val"], batch_size, h=h, **kw),
+           "valid_pos": score_edges(model, score_func, data["valid_pos"], batch_size, h=h, **kw),
+           "test_pos": score_edges(model, score_func, data["test_pos"], batch_size, h=h_test, test_set=True, **kw)}
+    neg_valid, neg_test = data["valid_neg"], data["test_neg"]
+    if _target_only(data, heart):
+        neg_valid = target_negatives(data["valid_pos"], neg_valid)
+        neg_test = target_negatives(data["test_pos"], neg_test)
+    if _negatives_layout(data, heart) == "rows":
+        out["valid_neg"] = score_negatives(model, score_func, neg_valid, batch_size, h=h, **kw)
+        out["test_neg"] = score_negatives(model, score_func, neg_test, batch_size, h=h_test, test_set=True, **kw)
     else:
-        neg_valid = score_edges(model, score_func, data["valid_neg"], batch_size, h=h)
-        neg_test = score_edges(model, score_func, data["test_neg"], batch_size, h=h_test, test_set=True)
-    return split_metrics(pos_train, pos_valid, neg_valid, pos_test, neg_test, k_list=k_list,
-                         layout="rows" if heart else "shared")
+        out["valid_neg"] = score_edges(model, score_func, neg_valid, batch_size, h=h, **kw)
+        out["test_neg"] = score_edges(model, score_func, neg_test, batch_size, h=h_test, test_set=True, **kw)
+    return out
+
+
+@torch.no_grad()
+def evaluate_model(model, score_func, data, batch_size: int = 32768, k_list=(100,), heart: bool = False) -> dict:
+    """The reference's ``test()`` / ``test_citation2()`` (testing.py:50-74, :124-161): the scores of ``score_splits``,
+    still on the device, handed to ``split_metrics``.  ``heart``: ``valid_neg`` / ``test_neg`` are [P, K, 2] per-positive
+    negatives (the citation2 metrics); ogbl-citation2 without ``heart``: [P, K] target ids, the same metrics; otherwise
+    [M, 2] shared ones.
+
+    Two deliberate differences to the reference, both pinned by tests/test_gpu_pipeline.py: HeaRT test negatives are
+    encoded on the test-time graph (see ``score_splits``), and the train column of ogbl-citation2 is computed from the
+    ``train_pos_val`` scores -- ``test_citation2`` scores them and then reports the VALIDATION positives in their place
+    (``pos_train_pred = pos_valid_pred.view(-1)``, testing.py:70), so its train column repeats its valid column."""
+    s = score_splits(model, score_func, data, batch_size, heart=heart)
+    return split_metrics(s["train_pos_val"], s["valid_pos"], s["valid_neg"], s["test_pos"], s["test_neg"], k_list=k_list,
+                         layout=_negatives_layout(data, heart))
 
 
 # Metrics by heuristic bin (src/train/eval.py:44-77 ``test_by_metric``, behind run.py's --bymetric / --percentile,

@@ -418,6 +418,11 @@ def encoder_train(model, adj_prop=None, test_set=False):
     a_hat = model._device_graph("prop", model._data_obj("adj", test_set) if adj_prop is None else adj_prop)
     # ---- encoder (node_encoder.py:35-44, other_models.py:61-76, link_transformer.py:127)
     x = model._features()
+    raw = model.data["x"]
+    if torch.is_grad_enabled() and isinstance(raw, torch.Tensor) and raw.requires_grad:
+        # a feature table that takes a gradient (the reference's ogbl-ddi ``x`` is an nn.Parameter, read_datasets.py:76):
+        # the first layer's backward then produces its input gradient like every later layer's
+        x = raw.to(model.device, torch.float32)
     x = F.dropout(x, p=model.node_encoder.feat_drop, training=True)
     for i, conv in enumerate(enc.convs):
         if enc.lns is not None and enc.relu and model._fusable(i, x.shape[1]) and 0.0 <= float(enc.dropout) < 1.0:

@@ -10,18 +10,23 @@ replaced by oracle/ref_shims.py, as in make_golden.py) and pointed at the genera
 reference's own ``get_ppr_matrix`` / ``create_sparse_ppr_matrix`` without the disk cache (``get_ppr`` writes under the
 reference tree, which is read-only).  Only DATA is written: the synthetic input files and the arrays the reference
 returned for them.  tests/test_readers.py::test_planetoid_reader_matches_the_reference_reader reads both."""
-import os
 import sys
-import types
 
-import numpy as np
-import torch
+sys.dont_write_bytecode = True   # nothing may be written into the reference tree
+
+import os      # noqa: E402
+import types   # noqa: E402
+
+import numpy as np   # noqa: E402
+import torch         # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
 sys.path.insert(0, "/root/reference/src")
 from oracle import ref_shims  # noqa: E402
+from reference_env import OGB_DIR, OGB_SPLIT, patch_reference_readers  # noqa: E402
 
 ref_shims.install()
 
@@ -73,11 +78,7 @@ def main():
     import util.read_datasets as rd
     rd.DATA_DIR = OUT_DIR
     rd.HEART_DIR = os.path.join(OUT_DIR, "heart")
-
-    def get_ppr_no_disk(dataset, edge_index, num_nodes, alpha, eps, is_val):
-        nb, w = cps.get_ppr_matrix(edge_index, num_nodes, alpha, eps)
-        return cps.create_sparse_ppr_matrix(nb, w).to_torch_sparse_coo_tensor()
-    rd.get_ppr = get_ppr_no_disk
+    patch_reference_readers(rd, cps)
     out = {}
     for heart in (False, True):
         args = types.SimpleNamespace(data_name=NAME, eps=1e-4, heart=heart)
@@ -106,11 +107,6 @@ def main():
 
 
 # ------------------------------------------------------------------------------------------------ OGB layouts
-OGB_DIR = os.path.join(HERE, "ogb_tiny")
-OGB_SPLIT = {"ogbl-collab": ("time", True), "ogbl-ppa": ("throughput", True), "ogbl-ddi": ("target", True),
-             "ogbl-citation2": ("time", False)}
-
-
 def _write_csv(path, arr, fmt):
     import gzip
     os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -180,67 +176,12 @@ def write_ogb_inputs():
             torch.save(torch.from_numpy(np.sort(rng.choice(te.shape[0], 30, replace=False))), os.path.join(hd, "test_samples_index.pt"))
 
 
-class _Data:
-    """What the reference touches of a PyG ``Data`` object (read_datasets.py:31-129)."""
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-    def to(self, device):
-        return self
-
-    def __getitem__(self, k):
-        return getattr(self, k)
-
-    def __setitem__(self, k, v):
-        setattr(self, k, v)
-
-
-class _OgbDataset:
-    """Stand-in for ``ogb.linkproppred.PygLinkPropPredDataset`` over the tiny raw files: the graph object as the OGB
-    package is DOCUMENTED to build it -- edge list from raw/edge.csv.gz with the inverse edges appended for the
-    undirected datasets (edge features repeated), float node features, [E, 1] edge attributes -- and the split
-    dictionaries of split/<type>/*.pt.  (The package itself is not available offline: this part of the pipeline -- files to
-    graph object -- stays an assumption of lpformer_amd/readers.py; everything the REFERENCE does with the object is what
-    this script records.)"""
-    def __init__(self, name):
-        import gzip
-        self.name = name
-        base = os.path.join(OGB_DIR, name.replace("-", "_"))
-        split_type, add_inverse = OGB_SPLIT[name]
-
-        def csv(fn, dt):
-            path = os.path.join(base, "raw", fn)
-            if not os.path.isfile(path):
-                return None
-            with gzip.open(path, "rt") as f:
-                return np.loadtxt(f, delimiter=",", dtype=dt, ndmin=2)
-        e = csv("edge.csv.gz", np.int64).T
-        n = int(csv("num-node-list.csv.gz", np.int64).reshape(-1)[0])
-        feat, w, yr = csv("node-feat.csv.gz", np.float32), csv("edge_weight.csv.gz", np.int64), csv("edge_year.csv.gz", np.int64)
-        rep = (lambda a: None if a is None else torch.from_numpy(np.concatenate([a, a]) if add_inverse else a))
-        ei = np.concatenate([e, e[::-1]], axis=1) if add_inverse else e
-        self._data = _Data(num_nodes=n, edge_index=torch.from_numpy(np.ascontiguousarray(ei)),
-                           x=None if feat is None else torch.from_numpy(feat), edge_weight=rep(w), edge_year=rep(yr))
-        self._split = {s: torch.load(os.path.join(base, "split", split_type, f"{s}.pt")) for s in ("train", "valid", "test")}
-
-    def __getitem__(self, i):
-        return self._data
-
-    def get_edge_split(self):
-        return self._split
-
-
 def main_ogb():
     write_ogb_inputs()
     import util.calc_ppr_scores as cps
     import util.read_datasets as rd
     rd.HEART_DIR = os.path.join(OGB_DIR, "heart")
-    rd.PygLinkPropPredDataset = lambda name: _OgbDataset(name)
-
-    def get_ppr_no_disk(dataset, edge_index, num_nodes, alpha, eps, is_val):
-        nb, w = cps.get_ppr_matrix(edge_index, num_nodes, alpha, eps)
-        return cps.create_sparse_ppr_matrix(nb, w).to_torch_sparse_coo_tensor()
-    rd.get_ppr = get_ppr_no_disk
+    patch_reference_readers(rd, cps)
     out = {}
     cases = [("ogbl-collab", True, False), ("ogbl-collab", False, False), ("ogbl-ppa", False, True), ("ogbl-ddi", False, True),
              ("ogbl-ddi", False, False), ("ogbl-citation2", False, False)]
