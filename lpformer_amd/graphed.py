@@ -20,6 +20,7 @@ from __future__ import annotations
 import torch
 
 from ._lib import check
+from .selection import SelectionWorkspace
 
 
 class GraphedScorer:
@@ -87,7 +88,7 @@ class GraphedScorer:
         raw = self.stream.cuda_stream
         self._keep = (model._z_cache, getattr(model, "_y_cache", None), getattr(model, "_zb_cache", None), model._folded,
                       getattr(model, "_tail_cache", None), getattr(model, "_score_fold_cache", None),
-                      [(k, w, getattr(w, "entries", None), getattr(w, "item_pair", None), getattr(w, "run_lb", None))
+                      [(k, w, w.buffers() if isinstance(w, SelectionWorkspace) else None)
                        for k, w in model._ws.items() if isinstance(k, tuple) and raw in k])
         self._key = self._param_key()
         self.captures += 1
@@ -188,7 +189,7 @@ class PlannedScorer(GraphedScorer):
         raw = self.stream.cuda_stream
         self._keep = (keep, model._z_cache, getattr(model, "_y_cache", None), getattr(model, "_zb_cache", None),
                       model._folded, getattr(model, "_tail_cache", None), getattr(model, "_score_fold_cache", None),
-                      [(k, w, getattr(w, "entries", None), getattr(w, "item_pair", None), getattr(w, "run_lb", None))
+                      [(k, w, w.buffers() if isinstance(w, SelectionWorkspace) else None)
                        for k, w in model._ws.items() if isinstance(k, tuple) and raw in k])
         self._key = self._param_key()
         self.captures += 1

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, fold, graph, mask_delta, ops, patterns
+from . import _lib, fold, graph, mask_delta, ops, patterns, selection
 from . import dist as lpf_dist
 from ._lib import FLAG_RELU, check, ptr
 from .ops import f32_rows, gemm, layernorm_, pad4, raw_stream
@@ -383,127 +383,7 @@ class LinkTransformerLayer(nn.Module):
         self.post_att_norm = nn.LayerNorm(out_dim * train_args["num_heads"])
 
 
-class _SelectWorkspace:
-    """Per (stream, batch size) buffers of the selection kernels (include/lpformer_hip.h, "Selection, second
-    generation").  ``ctl`` and the chained-scan words persist across launches (epoch-tagged, never cleared)."""
-
-    def __init__(self, device, bs: int):
-        self.device, self.bs = device, bs
-        self.plan_blocks = int(_lib.hip().lpf_select_plan_blocks(bs))
-        self.ctl = torch.zeros(_lib.CONST["LPF_SELECT_CTL_WORDS"], dtype=torch.int64, device=device)
-        self.desc = torch.empty(16 * max(bs, 1), dtype=torch.int64, device=device)
-        self.offs = torch.empty(bs + 1, dtype=torch.int64, device=device)
-        self.plan_lb = torch.zeros(self.plan_blocks + 1, dtype=torch.int64, device=device)
-        self.type_ptr = torch.zeros(3 * (bs + 1), dtype=torch.int32, device=device)
-        self.item_cap = self.ent_cap = 0
-        self.item_pair = self.run_lb = self.entries = None
-        self.calibrated = False
-
-    def ensure(self, item_cap: int, ent_cap: int, shrink: bool = False):
-        if item_cap > self.item_cap:
-            self.item_cap = int(item_cap)
-            self.item_pair = torch.empty(self.item_cap, dtype=torch.int32, device=self.device)
-            self.run_lb = torch.zeros(3 * self.item_cap, dtype=torch.int64, device=self.device)
-        if ent_cap > self.ent_cap or (shrink and ent_cap < self.ent_cap // 2):
-            self.ent_cap = int(ent_cap)
-            self.entries = None  # release before allocating the new size
-            self.entries = torch.empty(3 * self.ent_cap * 4, dtype=torch.int32, device=self.device)
-
-    def read_status(self, stream=None):
-        """(error bits, [n_cn, n_1hop, n_non1hop]) of the last batch.  The read is ordered after everything queued on
-        ``stream`` (a ``torch.cuda.Stream``; default: the current one): the copy is issued ON that stream and waited
-        for, so a selection kernel still in flight there cannot be read as "ok"."""
-        if stream is None:
-            v = self.ctl.tolist()
-        else:
-            with torch.cuda.stream(stream):
-                v = self.ctl.tolist()
-        return int(v[3]), [int(v[4]), int(v[5]), int(v[6])]
-
-    def clear_errors(self, stream=None):
-        """Clears the sticky bits on ``stream`` (default: the current one) -- the stream whose kernels raise them, so
-        the write cannot race with a kernel's atomicOr."""
-        if stream is None:
-            self.ctl[3] = 0
-        else:
-            with torch.cuda.stream(stream):
-                self.ctl[3] = 0
-
-
-class _Select4Workspace:
-    """Per (stream, batch size) buffers of the one-launch, pair-major selection (``lpf_select4``,
-    include/lpformer_hip.h): ``pair_tab`` int32 [bs, 4] = {first entry, n_cn, n_1hop, n_non1hop}, ``blk_cnt`` int32
-    [ceil(bs / 64)], ``entries`` 16-byte records.  ``ctl`` persists across launches (word 3: sticky error bits; word 0:
-    the room the last batch needed)."""
-
-    def __init__(self, device, bs: int):
-        self.device, self.bs = device, bs
-        self.ctl = torch.zeros(_lib.CONST["LPF_SELECT4_CTL_WORDS"], dtype=torch.int64, device=device)
-        self.pair_tab = torch.zeros(4 * max(bs, 1), dtype=torch.int32, device=device)
-        self.blk_cnt = torch.zeros(2 * ((bs + _lib.SELECT4_BLOCK - 1) // _lib.SELECT4_BLOCK) + 2, dtype=torch.int32,
-                                   device=device)   # {entries, pairs with entries} per block
-        self.ent_cap = 0
-        self.kept_cap = 0       # selected entries the attention's scratch is sized for (its units of 16)
-        self.entries = None
-        self.calibrated = False
-
-    def ensure(self, ent_cap: int, shrink: bool = False):
-        if ent_cap > self.ent_cap or (shrink and ent_cap < self.ent_cap // 2):
-            self.ent_cap = int(ent_cap)
-            self.entries = None  # release before allocating the new size
-            self.entries = torch.empty(self.ent_cap * 4, dtype=torch.int32, device=self.device)
-
-    def read_status(self, stream=None):
-        """(error bits, [entries the last batch needed room for]); the read is ordered behind ``stream`` (see
-        ``_SelectWorkspace.read_status``)."""
-        if stream is None:
-            v = self.ctl.tolist()
-        else:
-            with torch.cuda.stream(stream):
-                v = self.ctl.tolist()
-        return int(v[3]), [int(v[0])]
-
-    def clear_errors(self, stream=None):
-        if stream is None:
-            self.ctl[3] = 0
-        else:
-            with torch.cuda.stream(stream):
-                self.ctl[3] = 0
-
-    def kept(self) -> int:
-        """Selected entries of the last batch (synchronises)."""
-        return int(self.blk_cnt[:-2:2].sum().item())
-
-
-class _Select4RegionsWorkspace(_SelectWorkspace):
-    """``lpf_select4`` + ``lpf_select4_regions``: the one-launch selection for consumers of the TYPE-MAJOR form (the
-    matrix-core attention, the record-merging tail, ``lpf_select_export``).  Looks like a ``_SelectWorkspace`` to them
-    (``type_ptr``, ``entries``, ``ent_cap``, ``ctl`` with the sticky bits in word 3 and the totals per type in words
-    4-6); the pair-major half (``pair_tab``, ``blk_cnt``, ``blk_types``, ``entries4``) stays inside."""
-
-    def __init__(self, device, bs: int):
-        self.device, self.bs = device, bs
-        nblk = (bs + _lib.SELECT4_BLOCK - 1) // _lib.SELECT4_BLOCK
-        self.ctl = torch.zeros(_lib.CONST["LPF_SELECT4_CTL_WORDS"], dtype=torch.int64, device=device)
-        self.pair_tab = torch.zeros(4 * max(bs, 1), dtype=torch.int32, device=device)
-        self.blk_cnt = torch.zeros(2 * nblk + 2, dtype=torch.int32, device=device)
-        self.blk_types = torch.zeros(4 * nblk + 4, dtype=torch.int32, device=device)
-        self.type_ptr = torch.zeros(3 * (bs + 1), dtype=torch.int32, device=device)
-        self.ent_cap = self.ent_cap4 = self.item_cap = 0
-        self.entries = self.entries4 = self.item_pair = self.run_lb = None
-        self.calibrated = False
-
-    def ensure4(self, ent_cap4: int, shrink: bool = False):
-        if ent_cap4 > self.ent_cap4 or (shrink and ent_cap4 < self.ent_cap4 // 2):
-            self.ent_cap4 = int(ent_cap4)
-            self.entries4 = None
-            self.entries4 = torch.empty(self.ent_cap4 * 4, dtype=torch.int32, device=self.device)
-
-    def ensure(self, item_cap: int = 0, ent_cap: int = 0, shrink: bool = False):
-        if ent_cap > self.ent_cap or (shrink and ent_cap < self.ent_cap // 2):
-            self.ent_cap = int(ent_cap)
-            self.entries = None
-            self.entries = torch.empty(3 * self.ent_cap * 4, dtype=torch.int32, device=self.device)
+_Select4RegionsWorkspace = selection.RegionsWorkspace   # (the name tests/test_gpu_select4.py imports from this module)
 
 
 # ------------------------------------------------------------------------------------------ the model
@@ -1046,18 +926,18 @@ class LinkTransformer(nn.Module):
         return hit[1]
 
     # ---------------------------------------------------------------------------------- selection
-    def _sel_ws(self, st, bs: int, regions: Optional[bool] = None) -> "_SelectWorkspace":
+    def _sel_ws(self, st, bs: int, regions: Optional[bool] = None):
         """The type-major selection workspace of (stream, batch size); ``regions``: it must be (True) / must not be
         (False) the one behind ``lpf_select4`` -- a workspace of the other kind is replaced; None: whatever is there."""
         key = ("sel2", st, bs)
         ws = self._ws.get(key)
-        if ws is None or (regions is not None and isinstance(ws, _Select4RegionsWorkspace) != regions):
-            ws = self._ws[key] = (_Select4RegionsWorkspace if regions else _SelectWorkspace)(self.device, bs)
+        if ws is None or (regions is not None and isinstance(ws, selection.RegionsWorkspace) != regions):
+            ws = self._ws[key] = (selection.RegionsWorkspace if regions else selection.PlanRunWorkspace)(self.device, bs)
         return ws
 
     def _regions_launch(self, ws, batch, wi):
         """``lpf_select4`` + ``lpf_select4_regions`` on the current stream; no host sync."""
-        self._select4_launch(ws, batch, wi, regions=True)
+        self._select4_launch(ws, batch, wi)
         with KernelTimer.span("select_regions"):
             check(_lib.hip().lpf_select4_regions(batch.shape[1], ptr(ws.pair_tab), ptr(ws.blk_types), ptr(ws.entries4),
                                                  ws.ent_cap4, ptr(ws.type_ptr), ptr(ws.entries), ws.ent_cap, ptr(ws.ctl),
@@ -1067,31 +947,14 @@ class LinkTransformer(nn.Module):
         """True when the type-major consumers sit behind lpf_select4 + lpf_select4_regions."""
         return self.select4_regions and self.select_blocks and adj_mask is None and self.use_select_index
 
-    def _select_regions_device(self, batch: torch.Tensor, test_set: bool) -> "_Select4RegionsWorkspace":
-        """As ``_select_device`` for the walk-index path, through the one-launch selection: sized from earlier batches
-        (a block reserves its candidate slots in the pair-major buffer, the regions hold the kept entries), a batch that
-        does not fit raises the sticky bits (NaN scores, ``check_selection()`` sizes again), the first batch of a
-        (stream, batch size) is sized exactly with synchronisations."""
-        st = raw_stream(self.device)
-        bs = batch.shape[1]
-        ws = self._sel_ws(st, bs, regions=True)
+    def _select_regions_device(self, batch: torch.Tensor, test_set: bool) -> selection.RegionsWorkspace:
+        """As ``_select_device`` for the walk-index path, through the one-launch selection (a block reserves its
+        candidate slots in the pair-major buffer, the regions hold the kept entries)."""
+        ws = self._sel_ws(raw_stream(self.device), batch.shape[1], regions=True)
         wi = self._select_graphs(test_set, None)
         if not ws.calibrated:
-            ws.ensure4(16)
-            ws.ensure(ent_cap=16)
-            self._select4_launch(ws, batch, wi, regions=True)    # (token buffer: the kernel still reports the room it needs)
-            err, _ = ws.read_status()
-            need = int(ws.ctl[0].item())
-            ws.shape = self._select4_shape(bs, int(ws.ctl[1].item()))
-            ws.clear_errors()
-            if err & _lib.SELECT_ERR_NODE_RANGE:
-                raise IndexError(f"batch holds node ids outside [0, {self.num_nodes})")
-            ws.ensure4(3 * need + 65536, shrink=True)
-            self._regions_launch(ws, batch, wi)                  # (token regions: the totals per type come back)
-            _, tot = ws.read_status()
-            ws.clear_errors()
-            ws.ensure(ent_cap=2 * max(tot) + 4096, shrink=True)
-            ws.calibrated = True
+            ws.calibrate(self._select4_launch, self._regions_launch, batch, wi, num_nodes=self.num_nodes,
+                         shape=self._select4_shape)
         self._regions_launch(ws, batch, wi)
         return ws
 
@@ -1170,36 +1033,16 @@ class LinkTransformer(nn.Module):
         t0 = self._device_graph("t0", ppr_obj) if self.mask == "all" else None
         return adj, adjx, ppr, t0
 
-    def _select_device(self, batch: torch.Tensor, test_set: bool, adj_mask=None) -> "_SelectWorkspace":
+    def _select_device(self, batch: torch.Tensor, test_set: bool, adj_mask=None) -> selection.SelectionWorkspace:
         """Selection for the hot path: the result stays in the stream's workspace (per-type entry regions + int32
-        segment pointers), sized from earlier batches; nothing is read back.  A batch that does not fit raises the
-        sticky error bits in ``ws.ctl`` -- consumers clamp, the scores of such a batch come out as NaN, and
-        ``check_selection()`` (called by the evaluation sweep and by every API that synchronises anyway) grows the
-        workspace.  The first batch of a (stream, batch size) is sized exactly, with one synchronisation."""
+        segment pointers), nothing is read back; sizing, overflow and ``check_selection()`` (called by the evaluation
+        sweep and by every API that synchronises anyway) as lpformer_amd/selection.py describes."""
         if self._uses_select4_regions(adj_mask):
             return self._select_regions_device(batch, test_set)
-        st = raw_stream(self.device)
-        bs = batch.shape[1]
-        ws = self._sel_ws(st, bs, regions=False)
+        ws = self._sel_ws(raw_stream(self.device), batch.shape[1], regions=False)
         graphs = self._select_graphs(test_set, adj_mask)
         if not ws.calibrated:
-            # exact sizing, once (synchronises): the kernels count every selected entry even when the entry regions
-            # are too small to hold them, so one pass with token regions gives the totals
-            ws.ensure(item_cap=max(bs, 4096) + 16, ent_cap=16)
-            for _attempt in range(3):
-                self._select_launch(ws, batch, graphs)
-                items = int(ws.ctl[1].item())
-                err, tot = ws.read_status()
-                ws.clear_errors()
-                if err & _lib.SELECT_ERR_NODE_RANGE:
-                    raise IndexError(f"batch holds node ids outside [0, {self.num_nodes})")
-                if not (err & _lib.SELECT_ERR_ITEM_CAP):
-                    break
-                ws.ensure(item_cap=2 * items + 16, ent_cap=16)
-            else:
-                raise _lib.LpfError("selection workspace could not be sized")
-            ws.ensure(item_cap=2 * items + 16, ent_cap=2 * max(tot) + 4096, shrink=True)
-            ws.calibrated = True
+            ws.calibrate(self._select_launch, batch, graphs, num_nodes=self.num_nodes)
         self._select_launch(ws, batch, graphs)
         return ws
 
@@ -1245,16 +1088,17 @@ class LinkTransformer(nn.Module):
     S4_SHAPE_SLOTS = (2000, 6000)
 
     def _select4_shape(self, bs: int, slots: int) -> int:
-        nblk = (bs + _lib.SELECT4_BLOCK - 1) // _lib.SELECT4_BLOCK
+        nblk = selection.blocks(bs)
         n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
         lo, hi = self.S4_SHAPE_SLOTS
         return 512 if (nblk >= 2 * n_cu and lo <= slots / max(nblk, 1) <= hi) else 0
 
-    def _select4_launch(self, ws, batch, wi, regions: bool = False, q=None):
-        """``lpf_select4`` into ``ws`` (a ``_Select4Workspace``, or -- ``regions`` -- the pair-major half of a
-        ``_Select4RegionsWorkspace``).  ``q = (Y, out)``: ``lpf_select4_q``, which also leaves ``out[p] = Y[a] + Y[b]`` for
-        the pairs that kept an entry."""
+    def _select4_launch(self, ws, batch, wi, q=None):
+        """``lpf_select4`` into ``ws`` (a ``selection.PairMajorWorkspace``, or the pair-major half of a
+        ``selection.RegionsWorkspace``).  ``q = (Y, out)``: ``lpf_select4_q``, which also leaves ``out[p] = Y[a] + Y[b]``
+        for the pairs that kept an entry."""
         lib, st = _lib.hip(), raw_stream(self.device)
+        entries, ent_cap = ws.pair_major
         cn = 1 if self.mask == "cn" else 0
         name = "lpf_select4" if q is None else "lpf_select4_q"
         extra = () if q is None else (ptr(q[0]), q[0].stride(0), ptr(q[1]), q[1].stride(0), q[1].shape[1])
@@ -1263,37 +1107,20 @@ class LinkTransformer(nn.Module):
                                      ptr(wi.a1_cv), ptr(wi.px_cv), ptr(wi.t0_cv), ptr(wi.u.cv), ptr(wi.mini), cn,
                                      1 if wi.use_px else 0, float(self.thresh_cn), float(self.thresh_1hop),
                                      float(self.thresh_non1hop), ptr(ws.ctl), ptr(ws.pair_tab), ptr(ws.blk_cnt),
-                                     ptr(getattr(ws, "blk_types", None)), ptr(ws.entries4 if regions else ws.entries),
-                                     ws.ent_cap4 if regions else ws.ent_cap,
-                                     self.select4_threads or getattr(ws, "shape", 0), *extra, st), name)
+                                     ptr(getattr(ws, "blk_types", None)), ptr(entries), ent_cap,
+                                     self.select4_threads or ws.shape, *extra, st), name)
 
-    def _select4_device(self, batch: torch.Tensor, test_set: bool, q=None) -> "_Select4Workspace":
+    def _select4_device(self, batch: torch.Tensor, test_set: bool, q=None) -> selection.PairMajorWorkspace:
         """The one-launch selection for the hot path (``lpf_select4``): pair-major entries, a table entry per pair,
-        nothing read back.  The entry buffer is sized from earlier batches (a batch needs room for its candidate
-        slots, which the kernel reports in ``ctl[0]``); a batch that does not fit raises the sticky error bits, its
-        scores come out as NaN and ``check_selection()`` sizes the buffer again.  The first batch of a (stream, batch
-        size) is sized exactly, with one synchronisation."""
-        st = raw_stream(self.device)
-        bs = batch.shape[1]
-        key = ("sel4", st, bs)
+        nothing read back; a batch needs room for its candidate slots, which the kernel reports in
+        ``ctl[selection.CTL_ROOM]`` (sizing and overflow: lpformer_amd/selection.py)."""
+        key = ("sel4", raw_stream(self.device), batch.shape[1])
         ws = self._ws.get(key)
         if ws is None:
-            ws = self._ws[key] = _Select4Workspace(self.device, bs)
+            ws = self._ws[key] = selection.PairMajorWorkspace(self.device, key[2])
         wi = self._select_graphs(test_set, None)
         if not ws.calibrated:
-            ws.ensure(ent_cap=16)
-            self._select4_launch(ws, batch, wi)      # (token buffer: the kernel still reports the room it needs)
-            err, need = ws.read_status()
-            ws.shape = self._select4_shape(bs, int(ws.ctl[1].item()))
-            ws.clear_errors()
-            if err & _lib.SELECT_ERR_NODE_RANGE:
-                raise IndexError(f"batch holds node ids outside [0, {self.num_nodes})")
-            # a block's place is reserved for its candidate SLOTS (an upper bound of what it keeps): three times the
-            # first batch's, hub-heavy batches need several times the room of sparse ones
-            ws.ensure(ent_cap=3 * need[0] + 65536, shrink=True)
-            self._select4_launch(ws, batch, wi)
-            ws.kept_cap = 2 * ws.kept() + 65536
-            ws.calibrated = True
+            ws.calibrate(self._select4_launch, batch, wi, num_nodes=self.num_nodes, shape=self._select4_shape)
         self._select4_launch(ws, batch, wi, q=q)
         return ws
 
@@ -1305,20 +1132,9 @@ class LinkTransformer(nn.Module):
         the caller's current stream is: a lane that has not run yet cannot be read as "ok"."""
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
-        st = stream.cuda_stream
-        ok = True
-        for key, ws in list(self._ws.items()):
-            if not (isinstance(key, tuple) and key[0] in ("sel2", "sel4") and key[1] == st):
-                continue
-            err, _ = ws.read_status(stream)
-            if err == 0:
-                continue
-            ok = False
-            ws.clear_errors(stream)
-            if err & _lib.SELECT_ERR_NODE_RANGE:
-                raise IndexError(f"batch holds node ids outside [0, {self.num_nodes})")
-            ws.calibrated = False   # re-size on the next batch
-        return ok
+        mine = [ws for key, ws in list(self._ws.items())
+                if isinstance(ws, selection.SelectionWorkspace) and key[1] == stream.cuda_stream]
+        return all([ws.check(self.num_nodes, stream).err == 0 for ws in mine])     # (a list: every one is checked)
 
     def _prop_delta(self, obj):
         """A propagation-matrix override (the ``--mask-input`` loop, src/train/train_model.py:47-56) that is the resident
@@ -1458,15 +1274,12 @@ class LinkTransformer(nn.Module):
                     "sel_pa": empty_f, "sel_pb": empty_f, "feats": feats, "ldf": ldf}
         for _attempt in range(3):
             ws = self._select_device(batch, test_set, adj_mask)
-            err, tot = ws.read_status()
-            if err == 0:
+            status = ws.check(self.num_nodes)
+            if status.err == 0:     # (otherwise it did not fit: sized again for this batch)
                 break
-            ws.clear_errors()
-            if err & _lib.SELECT_ERR_NODE_RANGE:
-                raise IndexError(f"batch holds node ids outside [0, {self.num_nodes})")
-            ws.calibrated = False  # did not fit: size again for this batch
         else:
             raise _lib.LpfError("selection workspace could not be sized")
+        tot = status.totals
         cap = sum(tot)
         sel_pair = self._workspace("sel_pair", cap, torch.int32, st)
         sel_node = self._workspace("sel_node", cap, torch.int32, st)
@@ -1477,7 +1290,7 @@ class LinkTransformer(nn.Module):
                                         feats.data_ptr() + 4 * self.dim, ldf, self.count_dim, ptr(sel_pair),
                                         ptr(sel_node), ptr(sel_pa), ptr(sel_pb), st), "lpf_select_export")
         return {"bs": bs, "cap": max(cap, 1), "type_ptr": type_ptr, "sel_pair": sel_pair, "sel_node": sel_node,
-                "sel_pa": sel_pa, "sel_pb": sel_pb, "feats": feats, "ldf": ldf, "tot": tuple(int(v) for v in tot)}
+                "sel_pa": sel_pa, "sel_pb": sel_pb, "feats": feats, "ldf": ldf, "tot": tuple(tot)}
 
     def _prep_batch(self, batch) -> torch.Tensor:
         batch = torch.as_tensor(batch).to(self.device)

@@ -17,16 +17,19 @@ N_ISO = 20
 
 
 class Reach:
-    """Call counts of the watched C entry points (wrappers on the ``_lib.hip()`` object)."""
+    """Call counts of the watched C entry points (wrappers on the ``_lib.hip()`` object) and, in ``log``, their names in
+    the order the host called them."""
 
     def __init__(self, monkeypatch, names):
         self.calls = collections.Counter()
+        self.log = []
         lib = _lib.hip()
         for nm in names:
             fn = getattr(lib, nm)
 
             def wrap(*a, _fn=fn, _nm=nm):
                 self.calls[_nm] += 1
+                self.log.append(_nm)
                 return _fn(*a)
             monkeypatch.setattr(lib, nm, wrap)
 

@@ -5,7 +5,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import lpformer_amd
-from lpformer_amd import data as D
+from lpformer_amd import data as D, selection
 from lpformer_amd.profile import KernelTimer
 name = os.environ.get("LPF_CFG", "collab")
 cfg = D.CONFIGS[name]
@@ -21,8 +21,8 @@ batches = [torch.from_numpy(D.sample_pairs(ei, n, cfg["batch"], seed=1000 + i)).
 t0 = time.perf_counter()
 ws = model._select_device(batches[0], False, None)
 torch.cuda.synchronize()
-print(f"# {name}: first selection (index build + sizing) {time.perf_counter() - t0:.2f} s; slots {int(ws.ctl[0])}, "
-      f"items {int(ws.ctl[1])}, kept {[int(v) for v in ws.ctl[4:7]]}")
+print(f"# {name}: first selection (index build + sizing) {time.perf_counter() - t0:.2f} s; slots {int(ws.ctl[selection.CTL_ROOM])}, "
+      f"items {int(ws.ctl[selection.CTL_ITEMS])}, kept {[int(v) for v in ws.ctl[selection.CTL_TOTALS]]}")
 def digest(ws, bs):
     tp = ws.type_ptr.view(3, bs + 1).long()
     tot = tp[:, bs].tolist()
