@@ -12,14 +12,14 @@ Everything here is one-time data preparation (the reference's ``cached=True`` / 
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Optional
 
 import numpy as np
 import scipy.sparse as sp
 import torch
 
-from . import _lib, ops
+from . import _lib, mask_delta, ops
 
 
 @dataclass
@@ -47,6 +47,50 @@ class CSR:
         return torch.sparse_coo_tensor(idx, v, (self.n, self.n)).coalesce()
 
 
+class Structure:
+    """The tables that are functions of a CSR's structure (``rowptr``, ``col``, ``n``) alone, each made on first use.  Graphs
+    that differ only in their values share ONE of these (``DeviceCSR.with_values``): an override rebuilds none of them."""
+
+    def __init__(self, rowptr: torch.Tensor, col: torch.Tensor, n: int):
+        self.rowptr, self.col, self.n = rowptr, col, n
+        self._long_rows, self._row_order = {}, {}       # keys (lo, hi) and (lo, hi, pad_hubs)
+        self._edge_keys = self._transposed = None
+
+    def long_rows(self, lo: int = 0, hi=None):
+        """Hub rows (more than LPF_SPMM_LONG_ROW entries) of rows [lo, hi): int32 row ids relative to ``lo``, or None."""
+        key = (lo, self.n if hi is None else hi)
+        if key not in self._long_rows:
+            deg = self.rowptr[lo + 1:key[1] + 1] - self.rowptr[lo:key[1]]
+            rows = torch.nonzero(deg > _lib.CONST["LPF_SPMM_LONG_ROW"]).flatten().to(torch.int32)
+            self._long_rows[key] = rows if rows.numel() else None
+        return self._long_rows[key]
+
+    def row_order(self, lo: int, hi: int, pad_hubs: bool = False):
+        """``fused_row_order`` of rows [lo, hi): the one-launch layer's degree-ordered tiles and hub slices."""
+        key = (lo, hi, bool(pad_hubs))
+        if key not in self._row_order:
+            self._row_order[key] = fused_row_order(self.rowptr, lo, hi, pad_hubs=key[2])
+        return self._row_order[key]
+
+    def edge_keys(self) -> torch.Tensor:
+        """Sorted int64 keys row * n + col of the stored entries (``mask_delta.edge_keys``)."""
+        if self._edge_keys is None:
+            self._edge_keys = mask_delta.edge_keys(self.rowptr, self.col, self.n)
+        return self._edge_keys
+
+    def transposed(self):
+        """(structure of the transposed pattern, int64 permutation ``order``): entry k of the transposed graph is entry
+        ``order[k]`` of this one, so its values are ``val[order]``."""
+        if self._transposed is None:
+            n, dev = self.n, self.col.device
+            rows = torch.repeat_interleave(torch.arange(n, device=dev), self.rowptr[1:] - self.rowptr[:-1])
+            order = torch.argsort(self.col.long() * n + rows)                      # sort by (column, row)
+            rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(torch.bincount(self.col.long(), minlength=n), 0, out=rowptr[1:])
+            self._transposed = (Structure(rowptr, rows[order].to(torch.int32).contiguous(), n), order)
+        return self._transposed
+
+
 @dataclass
 class DeviceCSR:
     rowptr: torch.Tensor  # int64
@@ -54,10 +98,20 @@ class DeviceCSR:
     val: Optional[torch.Tensor]
     n: int
     host: Optional[CSR] = None
+    structure: Optional[Structure] = field(default=None, compare=False, repr=False)   # made here unless shared
+    raw_val: Optional[torch.Tensor] = field(default=None, compare=False, repr=False)  # what ``gcn_norm_device`` normalised
+
+    def __post_init__(self):
+        if self.structure is None:
+            self.structure = Structure(self.rowptr, self.col, self.n)
 
     @property
     def nnz(self) -> int:
         return int(self.col.numel())
+
+    def with_values(self, val, raw_val=None) -> "DeviceCSR":
+        """A graph of other values on this one's ``rowptr`` / ``col``, SHARING its ``Structure``."""
+        return DeviceCSR(self.rowptr, self.col, val, self.n, None, self.structure, raw_val)
 
     def to_host(self) -> CSR:
         """Host copy (cached): the arrays of indexes that were built on the device are downloaded on first use."""
@@ -252,6 +306,17 @@ def as_coo_device(obj, device):
     return None
 
 
+def as_coo_on(obj, device, values: bool = True):
+    """(row, col, val|None, n) as tensors on ``device``: ``as_coo_device``'s answer where ``obj`` lives there already, else
+    ``as_coo_numpy``'s arrays uploaded as they are (``values=False``: the indices only); its ``TypeError`` otherwise."""
+    coo = as_coo_device(obj, device)
+    if coo is None:
+        row, col, val, n = as_coo_numpy(obj)
+        coo = (*(None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device)
+                 for a in (row, col, val if values else None)), n)
+    return coo
+
+
 def csr_from_coo_device(row: torch.Tensor, col: torch.Tensor, val, n: int, keep_val: bool = True) -> DeviceCSR:
     """Device twin of ``csr_from_coo``: sorted CSR, duplicate entries summed (coalesce semantics)."""
     key = row.long() * n + col.long()
@@ -275,7 +340,7 @@ def gcn_structure_csr_device(row: torch.Tensor, col: torch.Tensor, val, n: int) 
 
 
 def gcn_norm_device(struct: DeviceCSR, stream=None) -> DeviceCSR:
-    """Run ``lpf_gcn_norm_csr`` on a structure from ``gcn_structure_csr``; returns a CSR sharing rowptr/col."""
+    """Run ``lpf_gcn_norm_csr`` on a structure from ``gcn_structure_csr``; returns a CSR sharing it (raw weights kept)."""
     dev = struct.rowptr.device
     w_out = torch.empty(struct.nnz, dtype=torch.float32, device=dev)
     dis = torch.empty(struct.n, dtype=torch.float32, device=dev)
@@ -283,9 +348,7 @@ def gcn_norm_device(struct: DeviceCSR, stream=None) -> DeviceCSR:
     _lib.check(_lib.hip().lpf_gcn_norm_csr(struct.n, _lib.ptr(struct.rowptr), _lib.ptr(struct.col),
                                             _lib.ptr(struct.val), _lib.ptr(w_out), _lib.ptr(dis), st),
                "lpf_gcn_norm_csr")
-    out = DeviceCSR(struct.rowptr, struct.col, w_out, struct.n, None)
-    out.__dict__["_struct_val"] = struct.val     # (the raw weights: an override that only drops edges re-normalises them)
-    return out
+    return struct.with_values(w_out, raw_val=struct.val)
 
 
 def ppr_filter_device(ppr: DeviceCSR, mode: int, theta: float) -> DeviceCSR:

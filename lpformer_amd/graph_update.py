@@ -568,16 +568,7 @@ def update_graph(model, add=None, remove=None, *, alpha: float = 0.15, eps: floa
                       full_above=full_above, verify=verify, stats=stats)
     stats["data_s"] = time.perf_counter() - t
     model.data = new
-    model._graphs.clear()
-    model._override.clear()
-    model._delta_cache = None
-    model._enc_cache = None
-    model._z_cache = model._y_cache = None
-    model._zb_cache = None
-    model._xb_cache = None
-    model._ws.clear()
-    model._drop_sample_state()
-    model._graph_epoch = getattr(model, "_graph_epoch", 0) + 1
+    model._drop_graph_state()
     if rebuild and model.device.type == "cuda":
         dev = model.device
 

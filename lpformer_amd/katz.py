@@ -49,7 +49,7 @@ WORKSPACE_MB = distance.WORKSPACE_MB
 # batch holds one endpoint k / 2 times, a recommend result shares its source) is not the whole launch.  Not measured.
 RUN_MAX = 64
 
-_GRAPH: dict = {}                     # per graph object (sources.per_object): max degree, E2 table, entry keys
+_GRAPH: dict = {}                     # per graph object (sources.per_object): max degree, E2 table
 
 
 # ---------------------------------------------------------------------------------------------------------- options
@@ -196,17 +196,6 @@ def graph_tables(g: graph.DeviceCSR) -> dict:
     return sources.per_object(_GRAPH, g, make)
 
 
-def _entry_keys(g: graph.DeviceCSR) -> torch.Tensor:
-    """row * n + col of every stored entry, ascending (the CSR's own order): what ``ignore_direct`` looks pairs up in.
-    Made on first use, kept with the graph's tables."""
-    tab = graph_tables(g)
-    if "keys" not in tab:
-        rows = torch.repeat_interleave(torch.arange(g.n, dtype=torch.int64, device=g.col.device),
-                                       g.rowptr[1:] - g.rowptr[:-1], output_size=g.col.numel())
-        tab["keys"] = rows * g.n + g.col.long()
-    return tab["keys"]
-
-
 def _units(g: graph.DeviceCSR, a: torch.Tensor, b: torch.Tensor, ignore_direct: bool):
     """Orient, sort and cut one launch's pairs on the device (fixed shapes: nothing is read back): (pairs int64 [2, m]
     -- row 0 the spread endpoint, row 1 the walk endpoint, sorted --, unit_ptr int32 [m + 1], order int64 [m] with
@@ -229,7 +218,7 @@ def _units(g: graph.DeviceCSR, a: torch.Tensor, b: torch.Tensor, ignore_direct: 
     s, t = torch.where(spread_a, a, b), torch.where(spread_a, b, a)
     own = torch.zeros(m, dtype=torch.bool, device=dev)
     if ignore_direct and g.col.numel():
-        keys = _entry_keys(g)
+        keys = g.structure.edge_keys()      # ascending (the CSR's own order), made once per structure
         q = s * n + t
         own = ok & (keys[torch.searchsorted(keys, q).clamp_(max=keys.numel() - 1)] == q)
     order = torch.argsort((s * 2 + own.long()) * (n + 1) + t)

@@ -597,9 +597,9 @@ class LinkTransformer(nn.Module):
                 raise ValueError("the PPR matrix needs values")
             # this package's own containers are sorted and coalesced already: upload as they are
             g = (obj if kind == "ppr" else graph.CSR(obj.rowptr, obj.col, None, obj.n)).to_device(dev)
-        elif kind in ("prop", "mask") and graph.as_coo_device(obj, dev) is not None:
+        elif kind in ("prop", "mask") and (coo := graph.as_coo_device(obj, dev)) is not None:
             # a graph that already lives on this GPU (the training loop's per-batch masked adjacency): stay there
-            row, col, val, n = graph.as_coo_device(obj, dev)
+            row, col, val, n = coo
             if kind == "prop":
                 g = graph.gcn_norm_device(graph.gcn_structure_csr_device(row, col, val, n))
             else:
@@ -765,11 +765,7 @@ class LinkTransformer(nn.Module):
         last = i == len(enc.convs) - 1
         b16 = self.encoder_precision == "bf16"
         lib, st = _lib.hip(), raw_stream(self.device)
-        cache = a_hat.__dict__.setdefault("_fused_order", {})
-        key = (lo, hi, b16)
-        if key not in cache:
-            cache[key] = graph.fused_row_order(a_hat.rowptr, lo, hi, pad_hubs=b16)
-        order, hubs, parts = cache[key]
+        order, hubs, parts = a_hat.structure.row_order(lo, hi, pad_hubs=b16)
         ln = enc.lns[i] if enc.lns is not None else None
         res = x[lo:hi] if enc.residual else None
         out = torch.empty(hi - lo, d, dtype=torch.float32, device=self.device)
@@ -1147,52 +1143,25 @@ class LinkTransformer(nn.Module):
         if own_obj is None or obj is own_obj or not (self.use_mask_delta or named):
             return None
         own = self._device_graph("prop", own_obj)
-        raw = own.__dict__.get("_struct_val")
-        if raw is None:
+        if own.raw_val is None:
             return None
-        keys = own.__dict__.get("_edge_keys")
-        if keys is None:
-            keys = own.__dict__["_edge_keys"] = mask_delta.edge_keys(own.rowptr, own.col, own.n)
-        if isinstance(obj, graph.RemovedEdges):
+        keys = own.structure.edge_keys()
+        if named:
             # the difference named (no tensor of all the kept edges was built): the removed edges' raw weights to 0
-            e = obj.edges if isinstance(obj.edges, torch.Tensor) else torch.as_tensor(np.asarray(obj.edges))
-            new_w = mask_delta.prop_weights_minus_edges(keys, raw, e.to(self.device), own.n)
-            return self._share_structure(own, new_w)
-        coo = graph.as_coo_device(obj, self.device)
-        if coo is None:
+            new_w = mask_delta.prop_weights_minus_edges(keys, own.raw_val, torch.as_tensor(obj.edges).to(self.device), own.n)
+        else:
             try:
-                row, col, val, nn = graph.as_coo_numpy(obj)
+                row, col, val, nn = graph.as_coo_on(obj, self.device)
             except TypeError:
                 return None
-            coo = (torch.from_numpy(np.ascontiguousarray(row)).to(self.device),
-                   torch.from_numpy(np.ascontiguousarray(col)).to(self.device),
-                   None if val is None else torch.from_numpy(np.ascontiguousarray(val)).to(self.device), nn)
-        if coo[3] != own.n:
-            return None
-        new_w = mask_delta.prop_weights_from_coo(keys, raw, coo[0], coo[1], coo[2], own.n)
-        if new_w is None:
-            return None
-        return self._share_structure(own, new_w)
-
-    @staticmethod
-    def _share_structure(own: graph.DeviceCSR, new_w: torch.Tensor) -> graph.DeviceCSR:
-        """The propagation matrix of raw weights ``new_w`` laid out on ``own``'s structure: normalised, sharing rowptr /
-        col, the one-launch layer's tiles and (train.py) the transposed structure."""
-        g = graph.gcn_norm_device(graph.DeviceCSR(own.rowptr, own.col, new_w, own.n, None))
-        for k in ("_fused_order", "_long_rows"):      # (functions of the structure alone: one dict for both graphs)
-            g.__dict__[k] = own.__dict__.setdefault(k, {})
-        if "_edge_keys" in own.__dict__:
-            g.__dict__["_edge_keys"] = own.__dict__["_edge_keys"]
-        g.__dict__["_structure_of"] = own
-        return g
+            new_w = None if nn != own.n else mask_delta.prop_weights_from_coo(keys, own.raw_val, row, col, val, own.n)
+            if new_w is None:
+                return None
+        return graph.gcn_norm_device(own.with_values(new_w))     # (normalised; rowptr / col and the Structure are own's)
 
     def _own_mask_keys(self, test_set: bool) -> torch.Tensor:
         """Sorted int64 keys row * N + col of the model's own typing adjacency (kept with its device graph)."""
-        g = self._device_graph("mask", self._data_obj("mask", test_set))
-        k = g.__dict__.get("_edge_keys")
-        if k is None:
-            k = g.__dict__["_edge_keys"] = mask_delta.edge_keys(g.rowptr, g.col, g.n)
-        return k
+        return self._device_graph("mask", self._data_obj("mask", test_set)).structure.edge_keys()
 
     def _mask_delta(self, adj_mask, test_set: bool):
         """The override as a difference to the model's own typing adjacency: sorted directed keys of the removed edges, or
@@ -1209,14 +1178,10 @@ class LinkTransformer(nn.Module):
         if isinstance(adj_mask, graph.RemovedEdges):
             rk = mask_delta.removed_from_edges(own, torch.as_tensor(adj_mask.edges).to(dev), n)
         else:
-            coo = graph.as_coo_device(adj_mask, dev)
-            if coo is None:     # (a host-side container: its indices go to the device once, nothing is sorted there)
-                row, col, _, nn = graph.as_coo_numpy(adj_mask)
-                coo = (torch.from_numpy(np.ascontiguousarray(row)).to(dev), torch.from_numpy(np.ascontiguousarray(col)).to(dev),
-                       None, nn)
-            if coo[3] != n:
-                raise ValueError(f"graph has {coo[3]} nodes, the model {n}")
-            rk = mask_delta.removed_from_coo(own, coo[0], coo[1], n, self.mask_delta_limit)
+            row, col, _, nn = graph.as_coo_on(adj_mask, dev, values=False)    # (a host container: uploaded, not sorted)
+            if nn != n:
+                raise ValueError(f"graph has {nn} nodes, the model {n}")
+            rk = mask_delta.removed_from_coo(own, row, col, n, self.mask_delta_limit)
         self._delta_cache = (adj_mask, test_set, rk)
         return rk
 
@@ -1398,6 +1363,15 @@ class LinkTransformer(nn.Module):
                 base += tot[t]
         self._sample_cache = (mask_obj, ppr_obj, out)
         return out
+
+    def _drop_graph_state(self):
+        """Forget everything derived from the graph objects of ``self.data`` (they were replaced; the list is spelled out
+        at ``graph_update.update_graph``).  ``_graph_epoch`` moves: a scorer recorded on the old graph raises."""
+        for held in (self._graphs, self._override, self._ws):
+            held.clear()
+        self._delta_cache = self._enc_cache = self._z_cache = self._y_cache = self._zb_cache = self._xb_cache = None
+        self._drop_sample_state()
+        self._graph_epoch = getattr(self, "_graph_epoch", 0) + 1
 
     def _drop_sample_state(self):
         """Forget the entry sample and what was decided from it (the select4 / select3 gate, the `auto` attention choice,

@@ -30,8 +30,10 @@ import torch
 
 
 def edge_keys(rowptr: torch.Tensor, col: torch.Tensor, n: int) -> torch.Tensor:
-    """Sorted int64 keys row * n + col of a CSR pattern with sorted columns."""
-    rows = torch.repeat_interleave(torch.arange(n, device=rowptr.device), rowptr[1:] - rowptr[:-1])
+    """Sorted int64 keys row * n + col of a CSR pattern with sorted columns (``col`` holds exactly the stored entries:
+    with the output size given, nothing is read back)."""
+    rows = torch.repeat_interleave(torch.arange(n, device=rowptr.device), rowptr[1:] - rowptr[:-1],
+                                   output_size=col.numel())
     return rows * n + col.long()
 
 

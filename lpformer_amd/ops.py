@@ -100,15 +100,8 @@ def pair_gather(x: torch.Tensor, batch: torch.Tensor, *, product=None, sum=None,
 
 def long_rows(a, lo: int = 0, hi=None):
     """Hub rows (more than LPF_SPMM_LONG_ROW entries) of rows [lo, hi) of the ``DeviceCSR`` ``a``, as int32 row ids
-    relative to ``lo``, or None when there is none; cached on the graph object itself, so the list lives exactly as
-    long as the graph it describes."""
-    key = (lo, a.n if hi is None else hi)
-    cache = a.__dict__.setdefault("_long_rows", {})
-    if key not in cache:
-        deg = a.rowptr[lo + 1:key[1] + 1] - a.rowptr[lo:key[1]]
-        rows = torch.nonzero(deg > _lib.CONST["LPF_SPMM_LONG_ROW"]).flatten().to(torch.int32)
-        cache[key] = rows if rows.numel() else None
-    return cache[key]
+    relative to ``lo``, or None when there is none; kept with the graph's ``Structure``, as long as that lives."""
+    return a.structure.long_rows(lo, hi)
 
 
 def spmm(a, t: torch.Tensor, lo: int = 0, hi=None, *, bias=None, ln=None, res=None, final_ln=None, relu=False,

@@ -61,13 +61,8 @@ class LPFormer(nn.Module):
         data["adj_mask"] = data["full_adj_mask"] = graph.mask_csr(ei, n, symmetric=True)
         data["ppr"] = data["ppr_test"] = ppr_matrix
         self.core.num_nodes = n
-        self.core._graphs.clear()
-        self.core._override.clear()
         self.core._x_cache = None
-        self.core._z_cache = None
-        self.core._y_cache = None
-        self.core._enc_cache = None
-        self.core._drop_sample_state()     # (the entry sample and the choices made from it belong to the old graph)
+        self.core._drop_graph_state()      # (a scorer recorded on the old graph raises on its next call)
         self._bound = key
 
     def forward(self, batch: torch.Tensor, x: torch.Tensor, edge_index: torch.Tensor, ppr_matrix) -> torch.Tensor:

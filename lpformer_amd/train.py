@@ -30,7 +30,7 @@ import weakref
 import torch
 import torch.nn.functional as F
 
-from . import _lib, graph, ops
+from . import _lib, graph, ops, sources
 from ._lib import check, ptr
 from .ops import f32_rows, gemm, raw_stream
 
@@ -124,33 +124,16 @@ def _spmm_plain(a: graph.DeviceCSR, h: torch.Tensor, bias=None) -> torch.Tensor:
     return ops.spmm(a, f32_rows(h), bias=bias)
 
 
+_at_cache: dict = {}
+
+
 def _transpose_csr(a: graph.DeviceCSR) -> graph.DeviceCSR:
-    """A^T as a device CSR (cached on ``a``): needed for the gradient of the aggregation."""
-    hit = a.__dict__.get("_transposed")
-    src = a.__dict__.get("_structure_of")
-    if hit is None and src is not None:
-        # an override that shares the resident graph's structure (LinkTransformer._prop_delta): the transposed structure
-        # and the permutation are the resident graph's, only the values are gathered again
-        t = _transpose_csr(src)
-        hit = a.__dict__["_transposed"] = graph.DeviceCSR(t.rowptr, t.col, a.val[src.__dict__["_transposed_order"]].contiguous(),
-                                                          a.n, None)
-        # functions of the structure alone -- the one-launch layer's degree-ordered tiles and hub slices, the long-row
-        # list of lpf_spmm_csr_f32 -- are the resident transposed graph's (recomputing them was a sort over the rows
-        # and a host synchronisation per batch: 1.7 of the 15 ms of a step that overrides the propagation matrix)
-        for k in ("_fused_order", "_long_rows"):
-            hit.__dict__[k] = t.__dict__.setdefault(k, {})
-    if hit is None:
-        n = a.n
-        rows = torch.repeat_interleave(torch.arange(n, device=a.col.device), a.rowptr[1:] - a.rowptr[:-1])
-        key = a.col.long() * n + rows                      # sort by (column, row)
-        order = torch.argsort(key)
-        counts = torch.bincount(a.col.long(), minlength=n)
-        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=a.col.device)
-        torch.cumsum(counts, 0, out=rowptr[1:])
-        hit = a.__dict__["_transposed"] = graph.DeviceCSR(rowptr, rows[order].to(torch.int32).contiguous(),
-                                                          a.val[order].contiguous(), n, None)
-        a.__dict__["_transposed_order"] = order
-    return hit
+    """A^T as a device CSR (kept per graph object), for the gradient of the aggregation.  The transposed STRUCTURE is
+    ``a.structure``'s: an override on the resident structure only gathers its values -- no sort, the resident tiles."""
+    def make():
+        t, order = a.structure.transposed()
+        return graph.DeviceCSR(t.rowptr, t.col, a.val[order].contiguous(), a.n, None, t)
+    return sources.per_object(_at_cache, a, make)
 
 
 class SpmmFn(torch.autograd.Function):
@@ -260,10 +243,7 @@ def _fused_layer(a: graph.DeviceCSR, x2: torch.Tensor, wp: torch.Tensor, bias=No
     through their slice sums first (csrc/gcn_fused.hip)."""
     n, d = a.n, x2.shape[1]
     lib, st = _lib.hip(), raw_stream(x2.device)
-    cache = a.__dict__.setdefault("_fused_order", {})
-    if (0, n) not in cache:
-        cache[(0, n)] = graph.fused_row_order(a.rowptr, 0, n)
-    order, hubs, parts = cache[(0, n)]
+    order, hubs, parts = a.structure.row_order(0, n)
     t_parts = None
     if hubs is not None:
         t_parts = torch.empty(parts.shape[0], d, dtype=torch.float32, device=x2.device)

@@ -528,6 +528,35 @@ def test_pyg_facade_recovers_from_selection_overflow():
     assert torch.equal(b, m(torch.from_numpy(dense.T.copy()).to(DEV), xt, et, data["ppr"]))
 
 
+def test_pyg_facade_rebind_forgets_the_old_graph():
+    """``forward`` with another graph rebinds the core: everything derived from the old graph objects goes (the mask-delta
+    cache, the workspaces, the uploads), a scorer recorded on the old graph RAISES on its next call instead of replaying
+    pointers into released indexes, and the logits are those of a facade that never saw the first graph."""
+    from lpformer_amd import _lib
+
+    def facade(state=None):
+        m = lpformer_amd.LPFormer(cfg["f_in"], cfg["dim"], num_gnn_layers=cfg["gnn_layers"],
+                                  ppr_thresholds=list(cfg["thresholds"]), device=DEV).to(DEV).eval()
+        if state is not None:
+            m.load_state_dict(state)
+        return m
+    cfg, n, ei, w, x, data, *_, batch = _setup("tiny", bs=512)
+    _, n2, ei2, _, x2, data2, *_, batch2 = _setup("tiny", scale=0.5, seed=5, bs=512)
+    tb, tb2 = torch.from_numpy(batch).to(DEV), torch.from_numpy(batch2).to(DEV)
+    m = facade()
+    first = m(tb, torch.from_numpy(x).to(DEV), torch.from_numpy(ei).to(DEV), data["ppr"])
+    plan = lpformer_amd.PlannedScorer(m.core, m.score, m.core.propagate(), tb, logits=True)
+    assert torch.equal(plan(tb), first)
+    m.core.compute_node_mask(tb, adj=lpformer_amd.RemovedEdges(tb[:, :8]))     # (fills the mask-delta cache)
+    assert m.core._delta_cache is not None and m.core._ws
+    got = m(tb2, torch.from_numpy(x2).to(DEV), torch.from_numpy(ei2).to(DEV), data2["ppr"])
+    assert m.core._delta_cache is None and m.core.num_nodes == n2 != n
+    with pytest.raises(_lib.LpfError):
+        plan(tb)
+    want = facade(m.state_dict())(tb2, torch.from_numpy(x2).to(DEV), torch.from_numpy(ei2).to(DEV), data2["ppr"])
+    assert (want - got).abs().max().item() <= 1e-6
+
+
 @pytest.mark.parametrize("world", [2, 3])
 def test_row_sharded_encoder_matches_unsharded(world):
     """The row-sharded encoder of every rank, emulated on one GPU (ragged N: not a multiple of the world size): per

@@ -276,6 +276,76 @@ def test_overrides_taken_as_differences_train_like_graphs_of_their_own():
             assert float((g1[k] - g0[k]).abs().max()) / scale <= 1e-5, k
 
 
+def test_second_step_with_a_fresh_override_rebuilds_nothing_structural(monkeypatch):
+    """Two training steps (backward included) on one model, each with FRESH override objects -- first the kept edges as a
+    ``coo()`` look-alike, then the removed edges named --: the second step's propagation override is another graph on the
+    resident ``graph.Structure``, so it calls ``graph.fused_row_order`` zero times (the first step calls it: the check
+    is not vacuous) and its backward pass transposes without sorting the edge list.  How "no sort" is detected:
+    ``train._transpose_csr`` is wrapped to mark the time spent inside it, ``torch.argsort`` -- the one sort a
+    transposition does -- is wrapped to count the calls made in that time, and every transposed graph the step got must
+    carry, by identity, the ``rowptr`` / ``col`` the first step's transposed graph had."""
+    from lpformer_amd import train
+    z, cfg = _load("train_step_d64")
+    n = cfg["n"]
+    ei, w = z["edge_index"].astype(np.int64), z["edge_weight"].astype(np.float32)
+    edges = torch.from_numpy(z["pos_edges"]).to(DEV)
+    neg = torch.from_numpy(z["neg_edges"]).to(DEV)
+    gone = np.concatenate([z["pos_edges"][0] * n + z["pos_edges"][1], z["pos_edges"][1] * n + z["pos_edges"][0]])
+    km = ~np.isin(ei[0] * n + ei[1], gone)
+    assert 0 < km.sum() < km.size
+
+    class _ST:
+        def __init__(self, v):
+            self._v = v
+
+        def coo(self):
+            return torch.from_numpy(ei[0][km]).to(DEV), torch.from_numpy(ei[1][km]).to(DEV), self._v
+
+        def sparse_sizes(self):
+            return (n, n)
+    model, score = _build(z, cfg)
+    model.train(); score.train()
+    seen = {"order": 0, "sorts": 0, "inside": 0, "transposed": []}
+    real_order, real_argsort, real_transpose = graph.fused_row_order, torch.argsort, train._transpose_csr
+
+    def transpose(a):
+        seen["inside"] += 1
+        try:
+            seen["transposed"].append(real_transpose(a))
+        finally:
+            seen["inside"] -= 1
+        return seen["transposed"][-1]
+
+    def argsort(*args, **kw):
+        seen["sorts"] += bool(seen["inside"])
+        return real_argsort(*args, **kw)
+
+    def order(*args, **kw):
+        seen["order"] += 1
+        return real_order(*args, **kw)
+    monkeypatch.setattr(train, "_transpose_csr", transpose)
+    monkeypatch.setattr(torch, "argsort", argsort)
+    monkeypatch.setattr(graph, "fused_row_order", order)
+
+    def step(ov_prop, ov_mask):
+        h = model(edges, adj_prop=ov_prop, adj_mask=ov_mask)
+        loss = (-torch.log(score(h) + 1e-6).mean() - torch.log(1 - score(model(neg)) + 1e-6).mean())
+        loss.backward()
+        return model._override["prop"][1]
+
+    g1 = step(_ST(torch.from_numpy(w[km]).to(DEV)), _ST(None))
+    first = dict(seen, transposed=list(seen["transposed"]))
+    assert first["order"] >= 1 and first["sorts"] >= 1 and first["transposed"]
+    seen.update(order=0, sorts=0, transposed=[])
+    g2 = step(lpformer_amd.RemovedEdges(edges), lpformer_amd.RemovedEdges(edges))
+    own = model._device_graph("prop", model.data["adj_t"])
+    assert g2 is not g1 and g2.structure is g1.structure is own.structure
+    assert seen["order"] == 0 and seen["sorts"] == 0
+    assert seen["transposed"]
+    for t in seen["transposed"]:
+        assert t.rowptr is first["transposed"][0].rowptr and t.col is first["transposed"][0].col
+
+
 @pytest.mark.parametrize("dim,drop_p,skip", [(128, 0.0, False), (64, 0.0, True), (32, 0.0, False), (128, 0.25, True),
                                              (64, 0.1, False), (32, 0.5, True)])
 def test_fused_layer_backward_matches_fp64_autograd(dim, drop_p, skip):

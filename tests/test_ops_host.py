@@ -73,10 +73,14 @@ def test_long_rows_is_computed_once_per_graph_and_block():
     a = _csr(DEGREES)
     first, block, none = ops.long_rows(a), ops.long_rows(a, 3, 5), ops.long_rows(a, 0, 2)
     assert ops.long_rows(a, 0, a.n) is first               # hi=None is the whole graph: one key
-    a.rowptr = None                                        # a second look at the degrees would raise
+    a.rowptr = a.structure.rowptr = None                   # a second look at the degrees would raise
     assert ops.long_rows(a) is first and ops.long_rows(a, 3, 5) is block
     assert ops.long_rows(a, 0, 2) is none is None          # "no hub row" is cached too
-    assert set(a.__dict__) == {"rowptr", "col", "val", "n", "host", "_long_rows"}     # one key on the graph object
+    # the graph object holds its declared fields and nothing else; of the holder's memos, one kind is filled
+    assert set(a.__dict__) == {"rowptr", "col", "val", "n", "host", "structure", "raw_val"}
+    assert set(vars(a.structure)) == {"rowptr", "col", "n", "_long_rows", "_row_order", "_edge_keys", "_transposed"}
+    assert set(a.structure._long_rows) == {(0, a.n), (3, 5), (0, 2)}
+    assert a.structure._row_order == {} and a.structure._edge_keys is None and a.structure._transposed is None
 
 
 def test_long_rows_threshold_is_the_headers(monkeypatch):
