@@ -69,27 +69,38 @@ class GraphedScorer:
         """True when a parameter (storage or version) or a precision switch changed since the capture."""
         return self._param_key() != self._key
 
-    def _capture(self):
-        model, dev = self.model, self.model.device
+    def _step(self) -> torch.Tensor:
+        """One eager ``score_pairs`` of the scorer's batch on the current stream."""
+        return self.model.score_pairs(self.batch, self.h, self.score_func, test_set=self.test_set, logits=self.logits)
+
+    def _warm_up(self):
+        """What precedes a capture or a recording: the parameters and the graph epoch the step is taken at, then eager
+        steps on the scorer's stream (ordered behind the caller's current one)."""
+        model = self.model
         self._params = list(model.parameters()) + list(self.score_func.parameters())
         self._graph_epoch = getattr(model, "_graph_epoch", 0)
-        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        self.stream.wait_stream(torch.cuda.current_stream(model.device))
         with torch.cuda.stream(self.stream):
             for _ in range(2):  # sizes the per-stream workspaces and fills every parameter-derived cache
-                model.score_pairs(self.batch, self.h, self.score_func, test_set=self.test_set, logits=self.logits)
+                self._step()
             if not model.check_selection(self.stream):   # (first call of a stream sizes exactly: cannot overflow)
-                model.score_pairs(self.batch, self.h, self.score_func, test_set=self.test_set, logits=self.logits)
+                self._step()
+
+    def _held(self):
+        """Strong references to everything the step's launches read or write outside the capture's or the recording's
+        own memory: the model's tables per encoder output and per parameter version, its workspaces of this stream."""
+        model, raw = self.model, self.stream.cuda_stream
+        return (model._z_cache, model._y_cache, model._zb_cache, model._folded, model._tail_cache, model._score_fold_cache,
+                [(k, w, w.buffers() if isinstance(w, SelectionWorkspace) else None)
+                 for k, w in model._ws.items() if isinstance(k, tuple) and raw in k])
+
+    def _capture(self):
+        self._warm_up()
         self.stream.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, stream=self.stream):
-            self.out = model.score_pairs(self.batch, self.h, self.score_func, test_set=self.test_set,
-                                         logits=self.logits)
-        # strong references to everything the captured launches read or write outside the graph's own pool
-        raw = self.stream.cuda_stream
-        self._keep = (model._z_cache, getattr(model, "_y_cache", None), getattr(model, "_zb_cache", None), model._folded,
-                      getattr(model, "_tail_cache", None), getattr(model, "_score_fold_cache", None),
-                      [(k, w, w.buffers() if isinstance(w, SelectionWorkspace) else None)
-                       for k, w in model._ws.items() if isinstance(k, tuple) and raw in k])
+            self.out = self._step()
+        self._keep = self._held()
         self._key = self._param_key()
         self.captures += 1
 
@@ -164,18 +175,10 @@ class PlannedScorer(GraphedScorer):
 
     def _capture(self):
         from . import _lib
-        model, dev = self.model, self.model.device
-        self._params = list(model.parameters()) + list(self.score_func.parameters())
-        self._graph_epoch = getattr(model, "_graph_epoch", 0)
-        self.stream.wait_stream(torch.cuda.current_stream(dev))
-        kw = dict(test_set=self.test_set, logits=self.logits)
+        self._warm_up()
         with torch.cuda.stream(self.stream):
-            for _ in range(2):  # sizes the per-stream workspaces and fills every parameter-derived cache
-                model.score_pairs(self.batch, self.h, self.score_func, **kw)
-            if not model.check_selection(self.stream):   # (first call of a stream sizes exactly: cannot overflow)
-                model.score_pairs(self.batch, self.h, self.score_func, **kw)
             with _lib.recording(_StepRecorder(self._SKIP)) as rec:
-                self.out = model.score_pairs(self.batch, self.h, self.score_func, **kw)
+                self.out = self._step()
             calls, keep = rec.calls, rec.kept
             want = self.out.clone()
         b = self.batch   # (its extent in memory: a [2, BS] window of a longer id list has its rows far apart)
@@ -186,11 +189,7 @@ class PlannedScorer(GraphedScorer):
         self._plan = [(name, fn, args, tuple(i for i, a in enumerate(args)
                                              if fn is not None and isinstance(a, int) and base <= a < base + nbytes))
                       for name, fn, args in calls]
-        raw = self.stream.cuda_stream
-        self._keep = (keep, model._z_cache, getattr(model, "_y_cache", None), getattr(model, "_zb_cache", None),
-                      model._folded, getattr(model, "_tail_cache", None), getattr(model, "_score_fold_cache", None),
-                      [(k, w, w.buffers() if isinstance(w, SelectionWorkspace) else None)
-                       for k, w in model._ws.items() if isinstance(k, tuple) and raw in k])
+        self._keep = (keep, *self._held())
         self._key = self._param_key()
         self.captures += 1
         self._replay(base)

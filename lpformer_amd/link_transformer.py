@@ -258,6 +258,7 @@ class mlp_score(nn.Module):  # noqa: N801  (name kept for drop-in compatibility)
         self._pads = [_PaddedLinear() for _ in self.lins]
         self._chain = DenseChain("dense_chain_score")
         self._chain_fold = DenseChain("dense_chain_score")  # folded first layer (LinkTransformer.score_pairs)
+        self._bias_key = self._bias_val = None   # (address, version) of the last bias and its value on the host (_tail)
 
     def _run(self, x: torch.Tensor, want_prob: bool) -> torch.Tensor:
         _require_gpu(x, "mlp_score.forward")
@@ -284,7 +285,7 @@ class mlp_score(nn.Module):  # noqa: N801  (name kept for drop-in compatibility)
             b = 0.0
             if last.bias is not None:  # scalar kernel argument: read it back only when the parameter changes
                 key = (last.bias.data_ptr(), last.bias._version)
-                if getattr(self, "_bias_key", None) != key:
+                if self._bias_key != key:
                     self._bias_key, self._bias_val = key, float(last.bias.detach().item())
                 b = self._bias_val
             check(_lib.hip().lpf_rowdot_sigmoid_f32(h.shape[0], h.shape[1], ptr(h), h.stride(0), ptr(w), b,
@@ -412,6 +413,7 @@ class LinkTransformer(nn.Module):
             self.mask = "1-hop"
         else:
             self.mask = "all"
+        self.n_types = {"all": 3, "1-hop": 2, "cn": 1}[self.mask]   # node types selected: CN, 1-hop, >1-hop
         self.dim = train_args["dim"]
         self.att_drop = train_args.get("att_drop", 0)
         self.num_layers = train_args["trans_layers"]
@@ -452,6 +454,19 @@ class LinkTransformer(nn.Module):
         self._ws = {}          # named workspaces
         self._param_list = None  # cached list(self.parameters()) for the fold key
         self._fold_memo = None   # the folded tables for the duration of one score_pairs call
+        self._zb_cache = None  # (Z, its bf16 copy)
+        self._xb_cache = None  # (weak reference to a fused bf16 layer's output, the bf16 image written beside it)
+        self._xb_feat = None   # (weak reference to the feature table, its version, its bf16 image)
+        self._sample_cache = None  # (adjacency object, PPR object, per type the (pa, pb) of the sample's entries)
+        self._pt_choice = None     # (parameter key, _patterns_pay's answer, refolds at the time)
+        self._auto_choice = None   # (parameter key, "flip" or "mfma" for attention_impl = "auto", refolds at the time)
+        self._pt_cache = None      # (_pattern_key, the activation-pattern tables)
+        self._flip_est = None      # (parameter key, (raw, left) of _flip_stats)
+        self._score_fold_cache = None  # (key, (A, c, kpad)) of the LAST score head folded (_score_fold)
+        self._tail_cache = None    # (key, device tables of the dense tail) (_tail_tables)
+        self._graph_epoch = 0      # moves when update_graph replaces the graphs: recorded scorers compare it
+        self._lanes = []           # persistent streams handed out by lanes()
+        self._last_att = None      # view of the last batch's post_att_norm(attention output) (explain, tests)
         self._chain_att = DenseChain("dense_chain_attn_out")   # attention output projection + post_att_norm
         self._chain_q = DenseChain("pair_q")                   # q = lin_l(x_a) + lin_l(x_b)
         self._conv_pads = [_PaddedLinear() for _ in self.node_encoder.gnn_encoder.convs]
@@ -659,18 +674,17 @@ class LinkTransformer(nn.Module):
         if self._folded is not None and self._folded[0] == key:
             return self._folded[1]
         sd = {k: v for k, v in self.state_dict().items()}
-        n_types = {"all": 3, "1-hop": 2, "cn": 1}[self.mask]
-        out = fold.fold_attention(sd, self.dim, n_types)
-        out["pe_tab"], out["pe_stat"] = fold.pe_tables(sd, self.dim, n_types)
-        out["flip_tab"], out["flip_base"], _, out["wfold_t"] = fold.flip_tables(sd, self.dim, n_types)
+        out = fold.fold_attention(sd, self.dim, self.n_types)
+        out["pe_tab"], out["pe_stat"] = fold.pe_tables(sd, self.dim, self.n_types)
+        out["flip_tab"], out["flip_base"], _, out["wfold_t"] = fold.flip_tables(sd, self.dim, self.n_types)
         # pe_stat[t][7]: the square of PPR value pairs inside which no unit flips (the pair-major kernel skips the look at
         # an entry's units there; the unit-major kernels never read the slot)
         out["pe_stat"] = out["pe_stat"].copy()
-        for t in range(n_types):
+        for t in range(self.n_types):
             out["pe_stat"][t, 7] = fold.no_flip_radius(out["flip_tab"][t], out["pe_stat"][t])
         dev = {k: torch.from_numpy(np.ascontiguousarray(v)).to(self.device) for k, v in out.items()}
         self._folded = (key, dev)
-        self._refolds = getattr(self, "_refolds", 0) + 1
+        self._refolds += 1
         self._z_cache = None
         self._y_cache = None      # (Y = X W_l^T + b_l is parameter-derived too: a stale Y would give stale queries)
         self._zb_cache = None
@@ -798,10 +812,10 @@ class LinkTransformer(nn.Module):
         """The bf16 image of a [N, D] fp32 table in the order ``lpf_gcn_layer_fused_bf16`` gathers from (element
         32 i + 8 q + 4 h + u = feature 16 (2 i + h) + 4 q + u): the one the previous fused layer wrote beside ``x``, or a
         torch permute + cast (the feature table: once per model; an all-gathered layer input: once per layer)."""
-        hit = getattr(self, "_xb_cache", None)
+        hit = self._xb_cache
         if hit is not None and hit[0]() is x:
             return hit[1]
-        feat = getattr(self, "_xb_feat", None)
+        feat = self._xb_feat
         if feat is not None and feat[0]() is x and feat[1] == x._version:
             return feat[2]
         n, d = x.shape
@@ -884,7 +898,7 @@ class LinkTransformer(nn.Module):
     def _node_y(self, x_node: torch.Tensor, w) -> torch.Tensor:
         """Y = X_node W_l^T + b_l, lin_l per node (cached like Z): with it q_pair = Y[a] + Y[b] -- literally the
         reference's expression (layers.py:212-215) -- is a gather-add per batch instead of a product."""
-        hit = getattr(self, "_y_cache", None)
+        hit = self._y_cache
         if hit is None or hit[0]() is not x_node or hit[1] != x_node._version:
             y = gemm(f32_rows(x_node), w["w_l"], w["b_l"], tag="gemm_node_query")
             torch.cuda.current_stream(self.device).synchronize()  # once per encoder output: other streams read Y
@@ -914,7 +928,7 @@ class LinkTransformer(nn.Module):
 
     def _z_bf16(self, z: torch.Tensor) -> torch.Tensor:
         """bf16 copy of the node table Z (once per encoder output; the storage format of the bf16 throughput mode)."""
-        hit = getattr(self, "_zb_cache", None)
+        hit = self._zb_cache
         if hit is None or hit[0] is not z:
             zb = z.to(torch.bfloat16).contiguous()
             torch.cuda.current_stream(self.device).synchronize()  # other streams read it
@@ -1063,16 +1077,23 @@ class LinkTransformer(nn.Module):
         selection on a sample + the table build, 0.2-0.3 s), with the same spacing as ``attention_kernel``'s estimate."""
         if self.dim < 128 or not (self.attention_rows and self.use_fused_attention):
             return True
+        return self._spaced_choice("_pt_choice", lambda: self._flip_stats()[1] <= self.PT_EXACT_MAX, True)
+
+    def _spaced_choice(self, slot: str, decide, while_training):
+        """A choice that costs a look at the weights (``decide()``: a 4,096-pair selection, counts read back), kept in
+        ``slot``: made once per parameter version in evaluation mode -- but at most once per ``flip_recheck_every`` versions
+        (a loop that alternates optimiser steps with scoring) and never while training (the last choice then, or
+        ``while_training`` before there is one; nothing is stored)."""
         self._fold()
-        last = getattr(self, "_pt_choice", None)        # (parameter key, choice, refolds at the time)
+        last = getattr(self, slot)
         if last is not None and (last[0] is self._folded[0] or self.training or
                                  self._refolds - last[2] < self.flip_recheck_every):
             return last[1]
         if self.training:
-            return True
-        ok = self._flip_stats()[1] <= self.PT_EXACT_MAX
-        self._pt_choice = (self._folded[0], ok, self._refolds)
-        return ok
+            return while_training
+        choice = decide()
+        setattr(self, slot, (self._folded[0], choice, self._refolds))
+        return choice
 
     # Launch shape of lpf_select4 from what the first batch of a (stream, batch size) showed (round 6, same-lease interleaved
     # A/B under the pipelined bench, profiles/r06_select4_shapes_pipelined.txt): where a batch gives every CU two
@@ -1205,16 +1226,27 @@ class LinkTransformer(nn.Module):
             return s
         pair, node, pa, pb, tp, counts = mask_delta.patch_selection(s, batch, rk, self.num_nodes, self.mask,
                                                                     self.thresh_1hop, self._ppr_lookup(test_set))
-        feats, d = s["feats"], self.dim
-        c = counts.to(torch.float32)
-        if self.count_dim == 4:
-            feats[:, d:d + 4] = torch.stack([c[0], c[1], c[2], c[0] + c[1]], dim=1)
-        elif self.count_dim == 3:
-            feats[:, d:d + 3] = torch.stack([c[0], c[1], c[0] + c[1]], dim=1)
-        else:
-            feats[:, d] = c[0]
+        feats = s["feats"]
+        feats[:, self.dim:self.dim + self.count_dim] = self._count_features(counts.to(torch.float32))
         return {"bs": bs, "cap": max(int(pair.numel()), 1), "type_ptr": tp, "sel_pair": pair, "sel_node": node,
                 "sel_pa": pa, "sel_pb": pb, "feats": feats, "ldf": s["ldf"]}
+
+    def _count_features(self, c: torch.Tensor) -> torch.Tensor:
+        """[BS, count_dim] count features (reference :170-177, 340-356) from the per-type counts ``c`` [3, BS]: n_cn,
+        n_1hop, n_non1hop, n_cn + n_1hop; mode "1-hop": without n_non1hop; mode "cn": n_cn alone."""
+        if self.count_dim == 4:
+            return torch.stack([c[0], c[1], c[2], c[0] + c[1]], dim=1)
+        if self.count_dim == 3:
+            return torch.stack([c[0], c[1], c[0] + c[1]], dim=1)
+        return c[0][:, None]
+
+    def _new_feats(self, bs: int) -> torch.Tensor:
+        """[BS, ld] fp32 for the rows [attention output | counts | pad]: the pad columns zero, the rest unwritten."""
+        used = self.dim + self.count_dim
+        feats = torch.empty(bs, pad4(used), dtype=torch.float32, device=self.device)
+        if feats.shape[1] > used:
+            feats[:, used:].zero_()
+        return feats
 
     def _select(self, batch: torch.Tensor, test_set: bool, adj_mask=None):
         """Selection in the REFERENCE layout (module-by-module path, compute_node_mask, attention weights): the two
@@ -1226,10 +1258,8 @@ class LinkTransformer(nn.Module):
                 return self._select_patched(batch, test_set, rk)
         lib, st = _lib.hip(), raw_stream(self.device)
         bs = batch.shape[1]
-        ldf = pad4(self.dim + self.count_dim)
-        feats = torch.empty(bs, ldf, dtype=torch.float32, device=self.device)  # [att out | counts | pad]
-        if ldf > self.dim + self.count_dim:
-            feats[:, self.dim + self.count_dim:].zero_()  # the attention output and the counts are written below
+        feats = self._new_feats(bs)    # (the attention output and the counts are written below)
+        ldf = feats.shape[1]
         type_ptr = self._workspace("type_ptr", 3 * (bs + 1), torch.int64, st)
         if bs == 0:
             type_ptr[:3].zero_()
@@ -1294,8 +1324,6 @@ class LinkTransformer(nn.Module):
     def lanes(self, k: int):
         """``k`` persistent HIP streams for pipelining independent batches (workspaces are kept per stream, so callers
         should reuse these instead of creating streams per sweep)."""
-        if not hasattr(self, "_lanes"):
-            self._lanes = []
         while len(self._lanes) < k:
             self._lanes.append(torch.cuda.Stream(self.device))
         return self._lanes[:k]
@@ -1312,6 +1340,31 @@ class LinkTransformer(nn.Module):
             side = self._side[main.cuda_stream] = torch.cuda.Stream(self.device)
         _lib.stream_wait(side, main)
         return side
+
+    def _on(self, side):
+        """``with self._on(side):`` launches go to ``side`` -- to the current stream when there is none."""
+        return torch.cuda.stream(side if side is not None else torch.cuda.current_stream(self.device))
+
+    def _join(self, side):
+        """The current stream waits for what was queued on ``side`` (q, the elementwise branch)."""
+        if side is not None:
+            _lib.stream_wait(torch.cuda.current_stream(self.device), side)
+
+    def _attention_front(self, batch, x_node, side, q, select, fork=False):
+        """What every form of the attention starts with, in this order: the folded tables, the node keys Z (with their
+        synchronisation, once per encoder output), the query where none was passed (``q`` None: ``_pair_q`` on ``side``,
+        or on the current stream), the selection's launches (``select()``) and the join of the side stream.  ``fork``: the
+        side stream is forked here, behind Z.  Returns (folded tables, Z, q, what ``select()`` returned)."""
+        w = self._fold()
+        z = self._node_keys(x_node, w)
+        if fork:
+            side = self._fork()
+        if q is None:   # (score_pairs has it gathered by the elementwise branch's launch)
+            with self._on(side):
+                q = self._pair_q(batch, x_node, w)
+        sel = select()
+        self._join(side)
+        return w, z, q, sel
 
     # Measured break-even of the two fp32 one-pass attention kernels, in mean flipped hidden units per selected entry
     # (tools/flip_breakeven.py, profiles/r04_flip_breakeven.txt): the cost of csrc/pair_flip.hip grows with the number
@@ -1337,7 +1390,7 @@ class LinkTransformer(nn.Module):
         PPR matrix and the thresholds, not of the weights: drawn once per model.  It decides which activation patterns
         are tabulated (``patterns.build``) and feeds ``flips_per_entry``; results never depend on it."""
         mask_obj, ppr_obj = self._data_obj("mask", False), self._data_obj("ppr", False)
-        hit = getattr(self, "_sample_cache", None)
+        hit = self._sample_cache
         if hit is not None and hit[0] is mask_obj and hit[1] is ppr_obj:
             return hit[2]
         if hit is not None:     # another graph / PPR matrix was bound: everything derived from the old sample goes with it
@@ -1358,7 +1411,7 @@ class LinkTransformer(nn.Module):
             bs = sel["bs"]
             tot = sel["type_ptr"][:3 * (bs + 1)].view(3, bs + 1)[:, bs].tolist()
             out, base = [None, None, None], 0
-            for t in range({"all": 3, "1-hop": 2, "cn": 1}[self.mask]):
+            for t in range(self.n_types):
                 out[t] = (sel["sel_pa"][base:base + tot[t]].clone(), sel["sel_pb"][base:base + tot[t]].clone())
                 base += tot[t]
         self._sample_cache = (mask_obj, ppr_obj, out)
@@ -1371,7 +1424,7 @@ class LinkTransformer(nn.Module):
             held.clear()
         self._delta_cache = self._enc_cache = self._z_cache = self._y_cache = self._zb_cache = self._xb_cache = None
         self._drop_sample_state()
-        self._graph_epoch = getattr(self, "_graph_epoch", 0) + 1
+        self._graph_epoch += 1
 
     def _drop_sample_state(self):
         """Forget the entry sample and what was decided from it (the select4 / select3 gate, the `auto` attention choice,
@@ -1391,13 +1444,12 @@ class LinkTransformer(nn.Module):
             # fold: an optimiser step that leaves them alone (frozen encoders, a score-head-only fine-tune) keeps them
             sample = self._entry_sample()
             key = self._pattern_key()
-            hit = getattr(self, "_pt_cache", None)
+            hit = self._pt_cache
             if hit is not None and hit[0] == key:
                 pt = hit[1]
             else:
-                n_types = {"all": 3, "1-hop": 2, "cn": 1}[self.mask]
                 sd = {k: v for k, v in self.state_dict().items()}
-                pt = patterns.build(sd, self.dim, n_types, sample, device=self.device)
+                pt = patterns.build(sd, self.dim, self.n_types, sample, device=self.device)
                 self._pt_cache = (key, pt)
             w["patterns"] = pt
         return pt
@@ -1424,14 +1476,14 @@ class LinkTransformer(nn.Module):
         entries whose patterns ``_pattern_tables`` does not hold (what the exact path of the kernel behind select4 has to
         find and correct one by one).  Once per parameter version."""
         w = self._fold()
-        hit = getattr(self, "_flip_est", None)
+        hit = self._flip_est
         if hit is not None and hit[0] is self._folded[0]:
             return hit[1]
         with torch.no_grad():
             sample = self._entry_sample()
             pt = self._pattern_tables(w) if self.dim >= 128 else None
             raw, left, total = 0.0, 0.0, 0
-            for t in range({"all": 3, "1-hop": 2, "cn": 1}[self.mask]):
+            for t in range(self.n_types):
                 pa, pb = sample[t]
                 total += pa.numel()
                 if pa.numel() == 0:
@@ -1478,19 +1530,8 @@ class LinkTransformer(nn.Module):
         if self.attention_impl == "auto":
             if self.dim < 128:
                 return "mfma"
-            # The estimate runs a 4,096-pair selection and reads counts back (host synchronisations): it is made once per
-            # parameter version in evaluation mode -- but not inside a loop that alternates optimiser steps with scoring
-            # (at most once per `flip_recheck_every` parameter versions), and never while training.
-            self._fold()
-            last = getattr(self, "_auto_choice", None)      # (parameter key, choice, refolds at the time)
-            if last is not None and (last[0] is self._folded[0] or self.training or
-                                     self._refolds - last[2] < self.flip_recheck_every):
-                return last[1]
-            if self.training:
-                return "flip"
-            choice = "flip" if self.flips_per_entry() <= self.flip_break_even() else "mfma"
-            self._auto_choice = (self._folded[0], choice, self._refolds)
-            return choice
+            return self._spaced_choice(
+                "_auto_choice", lambda: "flip" if self.flips_per_entry() <= self.flip_break_even() else "mfma", "flip")
         return self.attention_impl
 
     def _uses_rows(self) -> bool:
@@ -1505,9 +1546,7 @@ class LinkTransformer(nn.Module):
         selection's launch gathers the query itself, for the pairs that kept an entry."""
         lib, st, d = _lib.hip(), raw_stream(self.device), self.dim
         bs = batch.shape[1]
-        w = self._fold()
-        z = self._node_keys(x_node, w)
-        four = self._uses_select4(adj_mask)
+        four = self._uses_select4(adj_mask)     # (decided before the step began: _prepare_pair_major)
         q_sel = None
         if q_tab is not None:
             assert four and q is None and side is None
@@ -1515,12 +1554,9 @@ class LinkTransformer(nn.Module):
             #  read: the attention kernel fetches a query for pairs of entries, csrc/pair_rows.hip q_row)
             q = self._workspace("att_q", bs * d, torch.float32, st)[:bs * d].view(bs, d)
             q_sel = (q_tab, q)
-        if q is None:   # (score_pairs has it gathered by the elementwise branch's launch)
-            with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(self.device)):
-                q = self._pair_q(batch, x_node, w)
-        ws = self._select4_device(batch, test_set, q=q_sel) if four else self._select_device(batch, test_set, adj_mask)
-        if side is not None:
-            _lib.stream_wait(torch.cuda.current_stream(self.device), side)
+        w, z, q, ws = self._attention_front(
+            batch, x_node, side, q, lambda: (self._select4_device(batch, test_set, q=q_sel) if four
+                                             else self._select_device(batch, test_set, adj_mask)))
         layer = self.att_layers[0]
         units_cap = (ws.kept_cap + 15) // 16 + 1 if four else (3 * ws.ent_cap + 15) // 16 + 1
         pieces = self._workspace("att_pieces", units_cap * 2 * int(lib.lpf_pair_rows_piece_floats(d)), torch.float32, st)
@@ -1557,14 +1593,8 @@ class LinkTransformer(nn.Module):
         ``lpf_pair_attention_merge_f32``."""
         lib, st, d = _lib.hip(), raw_stream(self.device), self.dim
         bs = batch.shape[1]
-        w = self._fold()
-        z = self._node_keys(x_node, w)
-        if q is None:
-            with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(self.device)):
-                q = self._pair_q(batch, x_node, w)
-        ws = self._select_device(batch, test_set, adj_mask)
-        if side is not None:
-            _lib.stream_wait(torch.cuda.current_stream(self.device), side)
+        w, z, q, ws = self._attention_front(batch, x_node, side, q,
+                                            lambda: self._select_device(batch, test_set, adj_mask))
         rs = d + 4
         units_cap = (ws.ent_cap + 15) // 16 + 1
         part = self._workspace("att_part", 3 * bs * rs, torch.float32, st)
@@ -1593,15 +1623,8 @@ class LinkTransformer(nn.Module):
         ``torch.no_grad()`` with the model's device current."""
         lib, st, d = _lib.hip(), raw_stream(self.device), self.dim
         bs = batch.shape[1]
-        w = self._fold()
-        z = self._node_keys(x_node, w)
-        side = self._fork()
-        with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(self.device)):
-            q = self._pair_q(batch, x_node, w)
-
-        s = self._select(batch, test_set, adj_mask)
-        if side is not None:
-            _lib.stream_wait(torch.cuda.current_stream(self.device), side)  # q (and the elementwise branch) are done
+        w, z, q, s = self._attention_front(batch, x_node, None, None, lambda: self._select(batch, test_set, adj_mask),
+                                           fork=True)
         score = self._workspace("score", s["cap"], torch.float32, st)
         with KernelTimer.span("pair_scores"):
             check(lib.lpf_pair_scores_f32(d, ptr(s["type_ptr"]), bs, ptr(s["sel_pair"]), ptr(s["sel_node"]),
@@ -1620,15 +1643,11 @@ class LinkTransformer(nn.Module):
         with torch.no_grad():
             lib, st, d = _lib.hip(), raw_stream(self.device), self.dim
             bs = batch.shape[1]
-            if (d in (32, 64, 128, 256) and self.use_fused_attention and not return_weights and not stop_after_gather
-                    and bs > 0):
+            if self.use_fused_attention and not return_weights and not stop_after_gather and bs > 0:
                 # one-pass attention on the selection regions, then the records merged straight into the feature
                 # rows [post_att_norm(attention output) | counts] -- no reference-layout export, nothing read back
                 # (a batch that overflows the selection workspace comes back as NaN: check_selection())
-                ld = pad4(d + self.count_dim)
-                feats = torch.empty(bs, ld, dtype=torch.float32, device=self.device)
-                if ld > d + self.count_dim:
-                    feats[:, d + self.count_dim:].zero_()
+                feats = self._new_feats(bs)
                 layer = self.att_layers[0]
                 self._prepare_pair_major(adj_mask)
                 side = self._fork()
@@ -1641,7 +1660,7 @@ class LinkTransformer(nn.Module):
                     check(lib.lpf_pair_attention_merge_f32(
                         bs, d, self.count_dim, ptr(part), ptr(bnd), units_cap, ptr(ws.type_ptr),
                         ptr(layer.att.bias), ptr(layer.post_att_norm.weight), ptr(layer.post_att_norm.bias),
-                        ptr(ws.ctl), ptr(feats), ld, st), "lpf_pair_attention_merge_f32")
+                        ptr(ws.ctl), ptr(feats), feats.stride(0), st), "lpf_pair_attention_merge_f32")
                 self._last_att = feats[:, :d]
                 return feats, None, True   # (unchecked: calc_pairwise reads the status back after queueing its own work)
             s, score, z, w = self._pair_scores(batch, x_node, test_set, adj_mask)
@@ -1712,7 +1731,7 @@ class LinkTransformer(nn.Module):
               self.pairwise_lin.linears[1].weight, self.pairwise_lin.linears[1].bias,
               score_func.lins[0].weight, score_func.lins[0].bias]
         key = tuple((p.data_ptr(), p._version) for p in ps) + (id(score_func),)
-        hit = getattr(self, "_score_fold_cache", None)
+        hit = self._score_fold_cache
         if hit is not None and hit[0] == key:
             return hit[1]
         we1, be1, wp1, bp1, ws0, bs0 = (p.detach().double().cpu() for p in ps)
@@ -1732,7 +1751,7 @@ class LinkTransformer(nn.Module):
               pw.norm.weight, pw.norm.bias, score_func.lins[1].weight, score_func.lins[1].bias, layer.att.bias]
         self._fold()
         key = (tuple((p.data_ptr(), p._version) for p in ps), a.data_ptr(), self._folded[0])
-        hit = getattr(self, "_tail_cache", None)
+        hit = self._tail_cache
         if hit is not None and hit[0] == key:
             return hit[1]
         w = self._fold()
@@ -1785,7 +1804,7 @@ class LinkTransformer(nn.Module):
         """``lpf_select4_q`` -> ``lpf_pair_attention_rows4_f32`` -> ``lpf_tail_chain_rows_perm_ew_f32`` on the current
         stream: no buffer for r_e, no side stream.  None when the library has no such tail for this shape (the caller
         then takes the four-launch path; nothing this call queued is used)."""
-        lib, st, d = _lib.hip(), raw_stream(self.device), self.dim
+        st, d = raw_stream(self.device), self.dim
         bs = batch.shape[1]
         ew = self.elementwise_lin
         self._prepare_pair_major(None)
@@ -1794,18 +1813,32 @@ class LinkTransformer(nn.Module):
         rows = self._zero_workspace("att_rows", bs * (d + 4), st).view(bs, d + 4)   # (pad columns stay zero)
         ws, perm, nfull = self._attention_rows(batch, x_node, test_set, None, None, rows, self.count_dim, order=True,
                                                q_tab=y)
+        return self._tail_launch(
+            "lpf_tail_chain_rows_perm_ew_f32", score_func, a, c, bs, logits, None, lambda tt: (
+                (ptr(rows), rows.stride(0)),
+                (ptr(ws.ctl), ptr(perm), ptr(nfull), ptr(tt["bC_empty"]), ptr(tt["row_empty"]), ptr(x_node),
+                 x_node.stride(0), ptr(batch), batch.stride(0), x_node.shape[0], ptr(te["w1p"]), ptr(te["b1"]),
+                 ptr(te["ln_g"]), ptr(te["ln_b"]))), or_none=True)
+
+    def _tail_launch(self, name, score_func, a, c, bs, logits, r, own, or_none=False):
+        """The dense tail, entry point ``name`` of ``lpf_tail_chain_*``, on the current stream -> [BS] logits or
+        probabilities.  Each of them takes (BS, D, count_dim, arguments of its own, the shared block [first layer of
+        pairwise_lin | ``r`` = [r_e | r_p | pad], None where the tail computes r_e itself | folded score head], more of its
+        own, logit, prob, stream); ``own(tables)`` gives the two runs of its own, ``tables`` being ``_tail_tables``.
+        ``or_none``: None when the library has no instantiation of ``name`` for this shape (LPF_ERR_UNSUPPORTED)."""
         tt = self._tail_tables(score_func, a, c)
         res = torch.empty(bs, dtype=torch.float32, device=self.device)
+        sfx = "_bf16" if name.endswith("_bf16") else ""
+        head, tail = own(tt)
         with KernelTimer.span("tail_chain"):
-            rc = lib.lpf_tail_chain_rows_perm_ew_f32(
-                bs, d, self.count_dim, ptr(rows), rows.stride(0), ptr(tt["wB"]), ptr(tt["bB"]), ptr(tt["lnB_g"]),
-                ptr(tt["lnB_b"]), None, 0, ptr(tt["wC"]), ptr(tt["bC"]), ptr(tt["w_dot"]), ptr(tt["b_dot"]), ptr(ws.ctl),
-                ptr(perm), ptr(nfull), ptr(tt["bC_empty"]), ptr(tt["row_empty"]), ptr(x_node), x_node.stride(0),
-                ptr(batch), batch.stride(0), x_node.shape[0], ptr(te["w1p"]), ptr(te["b1"]), ptr(te["ln_g"]),
-                ptr(te["ln_b"]), ptr(res) if logits else None, None if logits else ptr(res), st)
-        if rc == _lib.CONST["LPF_ERR_UNSUPPORTED"]:
+            rc = getattr(_lib.hip(), name)(
+                bs, self.dim, self.count_dim, *head, ptr(tt["wB" + sfx]), ptr(tt["bB"]), ptr(tt["lnB_g"]),
+                ptr(tt["lnB_b"]), ptr(r), 0 if r is None else r.stride(0), ptr(tt["wC" + sfx]), ptr(tt["bC"]),
+                ptr(tt["w_dot"]), ptr(tt["b_dot"]), *tail, ptr(res) if logits else None, None if logits else ptr(res),
+                raw_stream(self.device))
+        if or_none and rc == _lib.CONST["LPF_ERR_UNSUPPORTED"]:
             return None
-        check(rc, "lpf_tail_chain_rows_perm_ew_f32")
+        check(rc, name)
         return res
 
     def _score_pairs_folded(self, batch, X_node, score_func, test_set, adj_mask, logits):
@@ -1816,7 +1849,8 @@ class LinkTransformer(nn.Module):
             x_node = f32_rows(X_node)
             a, c, kpad = self._score_fold(score_func)
             ew, pw = self.elementwise_lin, self.pairwise_lin
-            one_pass = d in (32, 64, 128, 256) and self.use_tail_chain and self.use_fused_attention and bs > 0
+            one_pass = self.use_tail_chain and self.use_fused_attention and bs > 0
+            tail_sfx = "_bf16" if self.tail_precision == "bf16" else "_f32"
             if one_pass and self._three_launches(x_node, adj_mask):
                 res = self._score_pairs_three(batch, x_node, score_func, test_set, a, c, logits)
                 if res is not None:
@@ -1830,7 +1864,7 @@ class LinkTransformer(nn.Module):
             if one_pass:
                 self._prepare_pair_major(adj_mask)
             side = self._fork()
-            with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(self.device)):
+            with self._on(side):
                 t = ew._chain1.tables(ew.linears[0].weight, ew.linears[0].bias, ew.norm.weight, ew.norm.bias)
                 if ew._chain1.run(t, x_node, relu=True, batch=batch, in_mode=1, out=r[:, :d], side=q_side) is None:
                     q_side = None
@@ -1838,13 +1872,12 @@ class LinkTransformer(nn.Module):
                     ops.pair_gather(x_node, batch, product=prod, tag="pair_gather")
                     gemm(prod, ew._pads[0].get(ew.linears[0].weight), ew.linears[0].bias, out=r[:, :d], tag="gemm")
                     layernorm_(r[:, :d], ew.norm.weight, ew.norm.bias, relu=True, tag="layernorm")
-            if (d in (32, 64, 128, 256) and self.use_tail_chain and self.use_fused_attention and bs > 0 and
-                    (self._uses_rows() or d == 256)):
+            if one_pass and (self._uses_rows() or d == 256):
                 # hot path: 2 selection launches (nothing read back) -> attention leaving finished rows -> the dense
                 # tail that is left: pairwise_lin's first layer, folded score head, sigmoid.  The rows come from the
                 # pair-major kernel or (D = 256 without it: the record-merging tail has no instantiation that wide) from
                 # the unit-major kernel + lpf_pair_attention_merge_f32
-                lib, st = _lib.hip(), raw_stream(self.device)
+                st = raw_stream(self.device)
                 order = None
                 if self._uses_rows():
                     rows = self._zero_workspace("att_rows", bs * (d + 4), st).view(bs, d + 4)   # (pad columns stay zero)
@@ -1857,53 +1890,27 @@ class LinkTransformer(nn.Module):
                 else:
                     rows, _, _ = self._pair_attention(batch, x_node, test_set, adj_mask, False)   # [BS, D + 4]
                     ws = self._sel_ws(st, bs)
-                tt = self._tail_tables(score_func, a, c)
-                res = torch.empty(bs, dtype=torch.float32, device=self.device)
-                with KernelTimer.span("tail_chain"):
-                    b16 = self.tail_precision == "bf16"
-                    # (behind select4 the attention kernel leaves no rows for pairs without selected nodes: the tail
-                    #  takes the constant row itself; behind select3 the rows are there and row_empty stays NULL)
-                    row0 = ptr(tt["row_empty"]) if (order and self._uses_select4(adj_mask)) else None
-                    extra = (ptr(order[0]), ptr(order[1]), ptr(tt["bC_empty"]), row0) if order else ()
-                    name = "lpf_tail_chain_rows" + ("_perm" if order else "") + ("_bf16" if b16 else "_f32")
-                    sfx = "_bf16" if b16 else ""
-                    check(getattr(lib, name)(
-                        bs, d, self.count_dim, ptr(rows), rows.stride(0), ptr(tt["wB" + sfx]),
-                        ptr(tt["bB"]), ptr(tt["lnB_g"]), ptr(tt["lnB_b"]), ptr(r), r.stride(0),
-                        ptr(tt["wC" + sfx]), ptr(tt["bC"]), ptr(tt["w_dot"]), ptr(tt["b_dot"]),
-                        ptr(ws.ctl), *extra, ptr(res) if logits else None, None if logits else ptr(res), st), name)
-                return res
-            if d in (32, 64, 128) and self.use_tail_chain and self.use_fused_attention and bs > 0:
+                # (behind select4 the attention kernel leaves no rows for pairs without selected nodes: the tail
+                #  takes the constant row itself; behind select3 the rows are there and row_empty stays NULL)
+                return self._tail_launch(
+                    "lpf_tail_chain_rows" + ("_perm" if order else "") + tail_sfx, score_func, a, c, bs, logits, r,
+                    lambda tt: ((ptr(rows), rows.stride(0)), (ptr(ws.ctl),) if not order else (
+                        ptr(ws.ctl), ptr(order[0]), ptr(order[1]), ptr(tt["bC_empty"]),
+                        ptr(tt["row_empty"]) if self._uses_select4(adj_mask) else None)))
+            if one_pass:
                 # 2 selection launches (nothing read back) -> one-pass attention (records) -> merged dense tail
-                lib, st = _lib.hip(), raw_stream(self.device)
                 ws, part, bnd, units_cap = self._fused_attention(batch, x_node, test_set, adj_mask, side,
                                                                  q=q_side and q_side[1])
-                tt = self._tail_tables(score_func, a, c)
-                res = torch.empty(bs, dtype=torch.float32, device=self.device)
-                with KernelTimer.span("tail_chain"):
-                    b16 = self.tail_precision == "bf16"
-                    name = "lpf_tail_chain_merge_bf16" if b16 else "lpf_tail_chain_merge_f32"
-                    check(getattr(lib, name)(
-                        bs, d, self.count_dim, ptr(part), ptr(bnd), units_cap, ptr(ws.type_ptr),
-                        ptr(self.att_layers[0].att.bias),
-                        ptr(tt["lnA_g"]), ptr(tt["lnA_b"]), ptr(tt["wB_bf16" if b16 else "wB"]), ptr(tt["bB"]),
-                        ptr(tt["lnB_g"]), ptr(tt["lnB_b"]), ptr(r), r.stride(0), ptr(tt["wC_bf16" if b16 else "wC"]),
-                        ptr(tt["bC"]), ptr(tt["w_dot"]),
-                        ptr(tt["b_dot"]), ptr(ws.ctl), ptr(res) if logits else None, None if logits else ptr(res),
-                        st), name)
-                return res
+                return self._tail_launch(
+                    "lpf_tail_chain_merge" + tail_sfx, score_func, a, c, bs, logits, r,
+                    lambda tt: ((ptr(part), ptr(bnd), units_cap, ptr(ws.type_ptr), ptr(self.att_layers[0].att.bias),
+                                 ptr(tt["lnA_g"]), ptr(tt["lnA_b"])), (ptr(ws.ctl),)))
             if d in (32, 64, 128) and self.use_tail_chain:  # attention output + pairwise hidden + head: one launch
                 g, feats, _ = self._pair_attention(batch, x_node, test_set, adj_mask, False, stop_after_gather=True)
-                tt = self._tail_tables(score_func, a, c)
-                res = torch.empty(bs, dtype=torch.float32, device=self.device)
-                with KernelTimer.span("tail_chain"):
-                    check(_lib.hip().lpf_tail_chain_f32(
-                        bs, d, self.count_dim, ptr(g), g.stride(0), ptr(tt["wA"]), ptr(tt["lnA_g"]), ptr(tt["lnA_b"]),
-                        feats.data_ptr() + 4 * d, feats.stride(0), ptr(tt["wB"]), ptr(tt["bB"]), ptr(tt["lnB_g"]),
-                        ptr(tt["lnB_b"]), ptr(r), r.stride(0), ptr(tt["wC"]), ptr(tt["bC"]), ptr(tt["w_dot"]),
-                        ptr(tt["b_dot"]), ptr(res) if logits else None, None if logits else ptr(res),
-                        raw_stream(self.device)), "lpf_tail_chain_f32")
-                return res
+                return self._tail_launch(
+                    "lpf_tail_chain_f32", score_func, a, c, bs, logits, r,
+                    lambda tt: ((ptr(g), g.stride(0), ptr(tt["wA"]), ptr(tt["lnA_g"]), ptr(tt["lnA_b"]),
+                                 feats.data_ptr() + 4 * d, feats.stride(0)), ()))
             feats, _, _ = self._pair_attention(batch, x_node, test_set, adj_mask, False)  # joins the side stream
             if kpad > d + pd:
                 r[:, d + pd:].zero_()
@@ -1989,7 +1996,7 @@ class LinkTransformer(nn.Module):
             x_node = f32_rows(X_node)
             comb = torch.empty(bs, 2 * d, dtype=torch.float32, device=self.device)
             side = self._fork()
-            with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(self.device)):
+            with self._on(side):
                 self.elementwise_lin.run(x_node, out=comb[:, :d], batch=batch, in_mode=1)
             _, attw = self.calc_pairwise(batch, x_node, test_set, adj_mask, return_weights, _out=comb[:, d:])
             return (comb, attw) if return_weights else comb

@@ -448,7 +448,6 @@ def pair_stage(model, x_node, batch, adj_mask=None, test_set=False, training: bo
         end_sort = (k.to(torch.int32), o)
     ew = _mlp(model.elementwise_lin, PairGatherFn.apply(x_node, batch, True, end_sort), training)  # x_a * x_b (:101-102)
     # ---- selection (integer work, no gradient) in the reference's layout, then the random attention drop
-    n_types = {"all": 3, "1-hop": 2, "cn": 1}[model.mask]
     with torch.no_grad():
         s = model._select(batch, test_set, adj_mask)
         tp = s["type_ptr"][:3 * (bs + 1)].view(3, bs + 1)
@@ -507,7 +506,7 @@ def pair_stage(model, x_node, batch, adj_mask=None, test_set=False, training: bo
         counts = cnt.float()
     # ---- positional encodings + attention (link_transformer.py:182-211, layers.py:161-224): dedicated kernels
     encoders = [model.ppr_encoder_cn, getattr(model, "ppr_encoder_onehop", None),
-                getattr(model, "ppr_encoder_non1hop", None)][:n_types]
+                getattr(model, "ppr_encoder_non1hop", None)][:model.n_types]
     heads = int(model.train_args["num_heads"])
     x_u = x_node.index_select(0, nodes_u)                           # rows of the batch's DISTINCT nodes
     w1s = torch.stack([e.linears[0].weight for e in encoders])
@@ -539,13 +538,7 @@ def pair_stage(model, x_node, batch, adj_mask=None, test_set=False, training: bo
         out = layer_norm(out, layer.post_att_norm.weight, layer.post_att_norm.bias)
         out = F.dropout(out, p=layer.dropout, training=training)
     # ---- count features + pairwise_lin (link_transformer.py:170-177, 340-356)
-    if n_types == 3:
-        cf = torch.stack([counts[0], counts[1], counts[2], counts[0] + counts[1]], dim=1)
-    elif n_types == 2:
-        cf = torch.stack([counts[0], counts[1], counts[0] + counts[1]], dim=1)
-    else:
-        cf = counts[0][:, None]
-    pw = _mlp(model.pairwise_lin, torch.cat([out, cf], dim=1), training)
+    pw = _mlp(model.pairwise_lin, torch.cat([out, model._count_features(counts)], dim=1), training)
     return ew, pw
 
 

@@ -533,3 +533,25 @@ def test_transposed_weight_cache_follows_the_parameter_object_and_its_version():
     n = len(train._wt_cache)
     v = torch.randn(4, 2)
     assert torch.equal(train._transposed(v), v.t()) and len(train._wt_cache) == n
+
+
+def test_every_private_attribute_a_method_reads_exists_after_construction():
+    """The runtime state of ``LinkTransformer`` and ``mlp_score`` is declared in ``__init__``: whatever ``self._name`` a
+    method of theirs loads is there right after construction (an attribute, a method or a property), so nothing in the
+    module has to ask with ``getattr(self, "_name", default)`` whether some other method has run yet."""
+    import ast
+    import inspect
+    from lpformer_amd import link_transformer as LT
+    fx = Fixture("lp_all_d64")
+    model = _model_for(fx)
+    score = lpformer_amd.mlp_score(model.out_dim, model.out_dim, 1, 2)
+    source = inspect.getsource(LT)
+    assert 'getattr(self, "_' not in source
+    classes = {c.name: c for c in ast.parse(source).body if isinstance(c, ast.ClassDef)}
+    for obj in (model, score):
+        loaded = {n.attr for n in ast.walk(classes[type(obj).__name__])
+                  if isinstance(n, ast.Attribute) and isinstance(n.ctx, ast.Load) and n.attr.startswith("_")
+                  and isinstance(n.value, ast.Name) and n.value.id == "self"}
+        assert len(loaded) > 5
+        missing = sorted(name for name in loaded if not hasattr(obj, name))
+        assert missing == [], f"{type(obj).__name__} reads these before anything has assigned them: {missing}"
