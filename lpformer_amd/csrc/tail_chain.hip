@@ -15,8 +15,9 @@
 //
 // Stage E (rows + perm form, fp32, D = 128: lpf_tail_chain_rows_perm_ew_f32) puts the elementwise branch in front:
 //   E  r_e = ReLU(LayerNorm( W_e0 (x_a * x_b) + b_e0 ))                  first layer of elementwise_lin
-// with the gathered B operand and the arithmetic of dense_chain.hip (in_mode 1), operation for operation.  r_e goes to
-// the hidden tiles and stage C's r_e half runs directly behind it -- the tiles are free again before stage A writes
+// with the arithmetic of dense_chain.hip (in_mode 1), operation for operation; the rows are gathered whole (8 adjacent
+// lanes per 128-byte line, every row once per workgroup) and the products reach the k-loop through the hidden tiles.
+// r_e goes to the hidden tiles and stage C's r_e half runs directly behind it -- the tiles are free again before stage A writes
 // them, so LDS does not grow --; its accumulators then live across stages A and B.  Order inside a workgroup:
 // E -> C over r_e -> (64 pairs without selected nodes: epilogue, done) -> A -> B -> C over r_p -> epilogue.  Stage C
 // sums in the order it always did (r_e k-groups first), so the scores are bitwise those of the separate launches.
@@ -189,10 +190,13 @@ __device__ __forceinline__ void tc_layernorm(f32x4 (&acc)[TPW], int fbase, int n
 __device__ uint64_t *tc_stamp_buf = nullptr;
 #define TC_STAMP(k) do { if (lane == 0) st_t[k] = wall_clock64(); } while (0)
 #define TC_STAMPS_OUT(kind) do { if (lane == 0 && tc_stamp_buf) { uint64_t *o__ = tc_stamp_buf + ((int64_t)blockIdx.x * TC_WAVES + wave) * 16; \
-        for (int k__ = 0; k__ < 8; ++k__) o__[k__] = st_t[k__]; o__[15] = (kind); } } while (0)
+        for (int k__ = 0; k__ < 10; ++k__) o__[k__] = st_t[k__]; o__[15] = (kind); } } while (0)
 // (16 words per wavefront: marks 0-6 as they always were, 7 = stage E done -- with it mark 4, C's r_e k-groups, comes
-//  BEFORE mark 1 --, word 15 = the kind)
+//  BEFORE mark 1 --, 8 = stage E's gathered rows have arrived (the stamped build waits for them there, vmcnt(0);
+//  the product build waits where the first use is), 9 = stage E's k-loop done, word 15 = the kind)
+#define TC_STAMP_ROWS() do { __builtin_amdgcn_s_waitcnt(0x0f70); TC_STAMP(8); } while (0)
 #else
+#define TC_STAMP_ROWS() do { } while (0)
 #define TC_STAMP(k) do { } while (0)
 #define TC_STAMPS_OUT(kind) do { } while (0)
 #endif
@@ -239,7 +243,7 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     f32x4 *my_hid = hid + (grp * S::HT) * 64 + lane;
     int buf = 0;
 #ifdef TC_STAMPS
-    uint64_t st_t[8] = {0};
+    uint64_t st_t[10] = {0};
     TC_STAMP(0);
 #endif
 
@@ -322,41 +326,63 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
         static_assert(ROWS && WM == 0 && S::PA == 1 && NTPA == NTA && NGE % 2 == 0 && 2 * tc_stage_stride(NTPA) <= S::SLAB &&
                           tc_stage_stride(2 * NTPA) == 2 * tc_stage_stride(NTPA), "stage E: the fp32 rows form at D = 128");
         // ------------------------------------------------------------------ stage E: first layer of elementwise_lin
-        // dense_chain.hip's layer 1 with in_mode 1: the B operand of k-group kg is X[a][16 kg + 4 q ..] * X[b][..]; a lane's
-        // sixteen 16-byte pieces of the two rows are requested at once, in front of the first k-group (the kernel's
-        // other stages need the registers only later), so the gather is one round trip, not one per k-group
-        int64_t ra = A.batch[mm], rb = A.batch[A.batch_ld + mm];
+        // dense_chain.hip's layer 1 with in_mode 1: the B operand of k-group kg is X[a][16 kg + 4 q ..] * X[b][..].  The
+        // rows are gathered whole, not in operand shape: a wavefront takes 8 of its group's 16 pairs (the wave pair splits
+        // them), 8 adjacent lanes per pair, and lane 8 jj + p reads the 16-byte piece p of each 128-byte line of the
+        // pair's two rows -- a load instruction touches 8 whole lines, and the wave pair no longer fetches every row
+        // twice: 8 loads per lane, all requested at once in front of the first k-group.  The products go to the
+        // (still free) hidden tiles in B-operand order and the k-loop reads them back: (kg, q, j) lies at
+        // kg TE_KG + (q >> 1) TE_Q2 + (q & 1) 16 + j.  The two strides are what keeps the banks apart: ds_read_b128
+        // serves lanes {0-3, 12-15, 20-27} .. together (j and 16 + j must differ mod 16: the (q & 1) 16), ds_write_b128
+        // 8 adjacent lanes -- here the 8 pieces (2 k-groups x 4 q) of one pair -- over 8 slots of 16 bytes: TE_KG = 4,
+        // TE_Q2 = 2 (mod 8) leave q and q ^ 1 on one slot, a 2-way conflict (16 LDS cycles against the 13 the store
+        // takes to hand over its registers), where the plain tiles would be 8-way.
+        constexpr int TE_KG = 68, TE_Q2 = 34;
+        static_assert((NGE - 1) * TE_KG + TE_Q2 + 32 <= S::HT * 64, "stage E's product tiles fit a group's hidden tiles");
+        const int gj = 8 * half + (lane >> 3), gp = lane & 7;       // pair of the group and piece of a line this lane gathers
+        const int64_t gpos = tile * (16 * TC_GROUPS) + grp * 16 + gj;
+        const int64_t gm = gpos < A.M ? gpos : A.M - 1;             // (a dead lane gathers what it would compute on)
+        const int64_t gmm = A.perm ? A.perm[gm] : gm;
+        int64_t ra = A.batch[gmm], rb = A.batch[A.batch_ld + gmm];
         WT wrE[2];
         tc_load<2, 2 * NTPA>(wrE, A.wE, 0, tid);
-        TC_PIN();   // (the first weights are requested next to the ids, not behind the sixteen pieces of the rows)
+        TC_PIN();   // (the first weights are requested next to the ids, not behind the eight pieces of the rows)
         if ((uint64_t)ra >= (uint64_t)A.n_rows) ra = 0;
         if ((uint64_t)rb >= (uint64_t)A.n_rows) rb = 0;
-        const float *xa = A.X + ra * A.ldX + 4 * q, *xb = A.X + rb * A.ldX + 4 * q;
+        const float *xa = A.X + ra * A.ldX + 4 * gp, *xb = A.X + rb * A.ldX + 4 * gp;
         f32x4 accE[TPWA];
 #pragma unroll
         for (int c = 0; c < TPWA; ++c) accE[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // (two k-groups per weight stage and barrier: a k-group of this layer is 512 float4, a slab holds 1,024; the
-        //  k-groups still reach an accumulator in ascending order)
-        f32x4 xra[NGE], xrb[NGE];
+        f32x4 xra[NGE / 2], xrb[NGE / 2];
 #pragma unroll
-        for (int kg = 0; kg < NGE; ++kg) {
-            xra[kg] = *reinterpret_cast<const f32x4 *>(xa + 16 * kg);
-            xrb[kg] = *reinterpret_cast<const f32x4 *>(xb + 16 * kg);
+        for (int i = 0; i < NGE / 2; ++i) {                         // line i of a row: k-groups 2 i and 2 i + 1
+            xra[i] = *reinterpret_cast<const f32x4 *>(xa + 32 * i);
+            xrb[i] = *reinterpret_cast<const f32x4 *>(xb + 32 * i);
         }
         tc_vec_publish();
+        TC_STAMP_ROWS();
+        {
+            f32x4 *pe = hid + (grp * S::HT) * 64 + (gp >> 2) * TE_KG + ((gp >> 1) & 1) * TE_Q2 + (gp & 1) * 16 + gj;
+#pragma unroll
+            for (int i = 0; i < NGE / 2; ++i) pe[2 * i * TE_KG] = xra[i] * xrb[i];
+        }
+        const f32x4 *my_pe = hid + (grp * S::HT) * 64 + (q >> 1) * TE_Q2 + (q & 1) * 16 + j;
+        // (two k-groups per weight stage and barrier: a k-group of this layer is 512 float4, a slab holds 1,024; the
+        //  k-groups still reach an accumulator in ascending order.  The first barrier also publishes the products.)
 #pragma unroll
         for (int kg = 0; kg < NGE; kg += 2) {
-            const f32x4 bv0 = xra[kg] * xrb[kg], bv1 = xra[kg + 1] * xrb[kg + 1];
             WT *lw = reinterpret_cast<WT *>(lds) + buf * S::SLAB;
             tc_store<2>(wrE, lw, tid);
             __syncthreads();
             if (kg + 2 < NGE) tc_load<2, 2 * NTPA>(wrE, A.wE, kg / 2 + 1, tid);
             TC_PIN();
+            const f32x4 bv0 = my_pe[kg * TE_KG], bv1 = my_pe[(kg + 1) * TE_KG];
             tc_mfma<TPWA>(accE, lw + (half * TPWA) * 64 + lane, bv0);
             tc_mfma<TPWA>(accE, lw + tc_stage_stride(NTPA) + (half * TPWA) * 64 + lane, bv1);
             TC_PIN();
             buf ^= 1;
         }
+        TC_STAMP(9);
         // stage A's rows: requested here, a LayerNorm and eight k-groups ahead of their use (the registers of the gathered
         // rows are free from here on), instead of one more round trip in front of stage B
         if (!lite) tc_rows_request();

@@ -1,7 +1,9 @@
 """Tuning aid: phase marks of tail_chain_kernel (build with EXTRA=-DTC_STAMPS): per wavefront start / stage A read /
 stage B k-groups done / LayerNorm B done / stage C r_e k-groups done / r_p k-groups done / end; in the three-launch step
 (model.fuse_step, the default at D = 128 fp32) also stage E done, and the r_e k-groups then come BEFORE the rows read.
-16 words per wavefront: marks 0-7, word 15 = the kind (0 full workgroup, 1 pairs without selected nodes)."""
+Stage E splits further: its gathered rows arrived (the stamped build waits for them there) / its k-loop done / its
+LayerNorm done (= stage E done).  16 words per wavefront: marks 0-9, word 15 = the kind (0 full workgroup, 1 pairs without
+selected nodes)."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -36,16 +38,17 @@ for i, b in enumerate(batches[:2]):
     v = v[v[:, 0] > 0]
     t0 = v[:, 0].min()
     ew = bool((v[:, 7] > 0).any())     # stage E form: start, E, C: r_e, rows read, stage B, LN B, C: r_p, end
-    order = [0, 7, 4, 1, 2, 3, 5, 6] if ew else list(range(7))
-    names = ["start", "rows read", "stage B loop", "LN B", "C: r_e loop", "C: r_p loop", "end", "stage E"]
+    order = [0, 8, 9, 7, 4, 1, 2, 3, 5, 6] if ew else list(range(7))
+    names = ["start", "rows read", "stage B loop", "LN B", "C: r_e loop", "C: r_p loop", "end", "stage E", "E: rows here",
+             "E: k-loop"]
     for kind, tag in ((0, "full workgroups"), (1, "workgroups of pairs without selected nodes")):
         s = v[v[:, 15] == kind]
         if not len(s):
             continue
-        rel = (s[:, :8] - t0) / 100.0
+        rel = (s[:, :10] - t0) / 100.0
         print(f"batch {i}, {tag}: {len(s)} wavefronts; last end {rel[:, 6].max():.1f} us")
         for k in order:
-            if kind == 1 and k not in ((0, 7, 4, 6) if ew else (0, 6)):
+            if kind == 1 and k not in ((0, 8, 9, 7, 4, 6) if ew else (0, 6)):
                 continue
             print(f"   {names[k]:14s} p10 {np.percentile(rel[:, k], 10):6.1f}  p50 {np.percentile(rel[:, k], 50):6.1f}  "
                   f"p90 {np.percentile(rel[:, k], 90):6.1f}  max {rel[:, k].max():6.1f}")
