@@ -427,6 +427,7 @@ def test_attention_stage_training_kernels_match_fp64_autograd(dim):
     pairs: empty pairs, pairs of 1 .. 3 entries (less than one trip of four), hub pairs of 37 and 130 entries, three
     types with different sizes, nodes shared by many entries (the dZ atomics)."""
     from lpformer_amd import train
+    from tests import train_kernel_reference as R
     torch.manual_seed(dim)
     rng = np.random.default_rng(dim)
     bs, n_nodes, n_t = 301, 500, 3
@@ -455,30 +456,9 @@ def test_attention_stage_training_kernels_match_fp64_autograd(dim):
     out = train.PairAttentionFn.apply(*params, e_node, e_pa, e_pb, torch.from_numpy(seg.reshape(-1)).to(DEV), tbase)
     (out * up).sum().backward()
     got = [p.grad.clone() for p in params]
-    # fp64 restatement
+    # fp64 restatement (tests/train_kernel_reference.py)
     P = [p.detach().double().requires_grad_() for p in params]
-    z_, q_, att_, bias_, wf_, bf_, w1_, b1_, g_, be_ = P
-    pair_of = np.zeros(n, np.int64)
-    type_of = np.zeros(n, np.int64)
-    for t in range(n_t):
-        for p in range(bs):
-            pair_of[seg[t, p]:seg[t, p + 1]] = p
-        type_of[tbase[t]:tbase[t + 1]] = t
-    pair_t, type_t = torch.from_numpy(pair_of).to(DEV), torch.from_numpy(type_of).to(DEV)
-    pa, pb = e_pa.double(), e_pb.double()
-
-    def hidden(x, y):
-        u = x[:, None] * w1_[type_t][:, :, 0] + y[:, None] * w1_[type_t][:, :, 1] + b1_[type_t]
-        mu, var = u.mean(1, keepdim=True), u.var(1, unbiased=False, keepdim=True)
-        return torch.relu((u - mu) / torch.sqrt(var + 1e-5) * g_[type_t] + be_[type_t])
-    h = hidden(pa, pb) + hidden(pb, pa)
-    kp = torch.einsum("ed,eod->eo", h, wf_[type_t]) + bf_[type_t]
-    k = z_[e_node.long()] + kp
-    s = (torch.nn.functional.leaky_relu(k * q_[pair_t], 0.2) * att_).sum(1)
-    smax = torch.full((bs,), -float("inf"), dtype=torch.float64, device=DEV).scatter_reduce(0, pair_t, s.detach(), "amax")
-    w = torch.exp(s - smax[pair_t])
-    den = torch.zeros(bs, dtype=torch.float64, device=DEV).index_add(0, pair_t, w) + 1e-16
-    ref = torch.zeros(bs, dim, dtype=torch.float64, device=DEV).index_add(0, pair_t, (w / den[pair_t])[:, None] * k) + bias_
+    ref = R.attention64(*P, e_node, e_pa.double(), e_pb.double(), R.pair_of_entries(seg, DEV), tbase)
     err = float((out.detach().double() - ref.detach()).abs().max())
     assert err <= 2e-5 * max(1.0, float(ref.detach().abs().max())), err
     (ref * up.double()).sum().backward()
