@@ -1052,6 +1052,44 @@ int lpf_pair_walks(int64_t m, int64_t n, const int64_t *pairs, int64_t pair_stri
                    void *workspace, int64_t n_groups, int64_t *walks_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Pair hop counts (pair_hops.hip): how many nodes sit at distance i from one endpoint and distance j from the other --
+ * what there was to select around a pair, per node class, and number for number the structure features A[d_a, d_b] and
+ * B[d] that ELPH / BUDDY estimate with sketches.  The reference has no such code.  Both symbols were added within
+ * ABI 16: the addition changes no existing symbol, so LPF_ABI_VERSION stays.
+ * ---------------------------------------------------------------------------------------------- */
+/* Bytes of workspace for n_groups resident workgroups: a 16-byte header (the unit ticket), then per group two 32-bit
+ * words per node (one for the spread endpoint's state, one for the walk endpoint's; each a 30-bit epoch stamp over a
+ * 2-bit payload): 16 + n_groups * 8 n. */
+int64_t lpf_pair_hop_counts_workspace_bytes(int64_t n, int64_t n_groups);
+/* The CSR has sorted, unique columns and a SYMMETRIC pattern (values ignored; a non-symmetric pattern is outside the
+ * contract).  hops = k is 1 or 2.  For an endpoint u, cls_u(v) = d(u, v) if that is <= k, else k + 1 (farther than k,
+ * or unreachable).  Stored self-loops change nothing; s == t is no special case (a diagonal table).
+ * The caller hands the m pairs over ORIENTED and GROUPED exactly as for lpf_pair_walks: pair j = (s, t) =
+ * (pairs[j], pairs[pair_stride + j]), unit_ptr int32[m + 1] cuts the list into units of one s each, the entries after
+ * the last unit's end hold m.  table_out int32[m][k + 2][k + 2]: cell [i][j] of pair j =
+ * |{v in [0, n) : cls_s(v) = i and cls_t(v) = j}|, the far/far cell [k + 1][k + 1] included, so a table sums to n; a
+ * pair with an id outside [0, n) gets an all-zero table; pairs no unit covers are left untouched.  (t, s) gives the
+ * transposed table: a caller that oriented a pair the other way round transposes it back.
+ * Persistent 256-thread workgroups take units by an atomic ticket, spread s once per unit k hops into dense
+ * epoch-stamped state over all n nodes (one unsigned integer atomic max per touch, which leaves a node's smallest
+ * distance in any order) and expand each pair's t k hops into a second such state under a per-pair epoch; the lane
+ * whose atomic max raised a word moves the node from the tally of its old class to that of its new one, which telescopes to
+ * the node's final class in any order.  The far row and column follow from the class sizes (counted from the rows and
+ * from the first touches of an epoch), the far/far cell from n.
+ * ignore_direct != 0: for a pair that is a unit of its own, the transitions {s, t} are skipped, which is taking
+ * distances on a copy of the graph without the stored entries (s, t) and (t, s); the caller makes every pair that is a
+ * stored entry a one-pair unit (a pair that is no entry is unaffected wherever it stands).
+ * The result is a pure function of (graph, pair, options): not of the position, the units, n_groups or timing; two runs
+ * are bitwise equal.  Integers only.
+ * workspace: lpf_pair_hop_counts_workspace_bytes(n, n_groups) bytes, 16-byte aligned; header and state are zeroed
+ * here, once per call.  1 <= hops <= 2 and 1 <= n_groups <= 65535 (checked first: LPF_ERR_INVALID whatever m is);
+ * m < 2^30 (the epoch stamps are 30 bits wide and a workgroup may take every unit and every pair), n < 2^31 - 3.
+ * m == 0 returns LPF_OK without a launch. */
+int lpf_pair_hop_counts(int64_t m, int64_t n, const int64_t *pairs, int64_t pair_stride, const int64_t *rowptr,
+                        const int32_t *col, int32_t hops, int32_t ignore_direct, const int32_t *unit_ptr,
+                        void *workspace, int64_t n_groups, int32_t *table_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Uniform negatives that avoid known edges (neg_sample.hip): K targets per source, or node pairs, drawn on the device
  * against a "known" CSR with sorted, unique int32 columns in [0, n) (values ignored; the pattern need not be
  * symmetric).  The reference draws torch.randint pairs (src/train/train_model.py:64) and has no edge-aware sampler.

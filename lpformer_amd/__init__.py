@@ -12,6 +12,10 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
                                         metrics_by_bin / attention_profile
     pair_walks, pair_katz               walk counts (A^l)[a, b], l <= 4, per pair (device meet-in-the-middle kernel) and
                                         the truncated Katz index; katz_from_walks, walks_reference (numpy restatement)
+    pair_hop_counts                     nodes by distance to both endpoints, int32 [P, k+2, k+2] per pair, k <= 2
+                                        (device spread-and-expand kernel): what there was to select, per node class;
+                                        elph_features (the ELPH / BUDDY layout), ball_jaccard, hop_counts_reference
+                                        (numpy restatement)
     recommend                           top-K new links per source node (device candidates, scoring, top-K)
     explain, explain_from_scores        per-pair attention attribution: top nodes, mass per type, entropy (device
                                         segmented reduction); pairs_of (a recommend result's pairs), attention_profile
@@ -37,6 +41,7 @@ from .graph import RemovedEdges  # noqa: F401
 from .graph_update import ppr_affected_sources, update_data, update_graph, update_ppr  # noqa: F401
 from .hard_negatives import HardNegatives, heart_negatives, twohop_rows  # noqa: F401
 from .heuristics import pair_heuristics  # noqa: F401
+from .hops import ball_jaccard, elph_features, hop_counts_reference, pair_hop_counts  # noqa: F401
 from .katz import katz_from_walks, pair_katz, pair_walks, walks_reference  # noqa: F401
 from .negatives import UniformNegatives, negative_pairs, negative_rows, negatives_reference  # noqa: F401
 from .graphed import GraphedScorer, PlannedScorer  # noqa: F401
@@ -53,4 +58,5 @@ __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_
            "pairs_of", "attention_profile", "Explanation", "threshold_profile", "suggest_thresholds", "ThresholdProfile",
            "TrainEdges", "train_epoch", "fit", "pair_distance", "DIST_BINS", "pair_walks",
            "pair_katz", "katz_from_walks", "walks_reference", "negative_rows", "negative_pairs", "UniformNegatives",
-           "negatives_reference", "link_split"]
+           "negatives_reference", "link_split", "pair_hop_counts", "hop_counts_reference", "elph_features",
+           "ball_jaccard"]
