@@ -1135,6 +1135,36 @@ int lpf_negative_pairs(int64_t M, int64_t n, const int64_t *rowptr, const int32_
                        int64_t pair_stride, int64_t *unresolved, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Bootstrap replicates of column sums (bootstrap.hip): what confidence intervals and paired tests of the ranking
+ * metrics are made of -- every metric but AP is a sum over positives of a per-positive value, so a bootstrap replicate
+ * is a sum of P gathered table rows, not a re-ranking.  The reference has no such code (it repeats runs).  Both symbols
+ * were added within ABI 16: the addition changes no existing symbol, so LPF_ABI_VERSION stays.
+ *
+ * icols int64 [P][Ci] and fcols double [P][Cf], row-major (one row is one gather); isum int64 [B][Ci], fsum double
+ * [B][Cf].  For r = 0 .. B - 1 and replicate b = b0 + r:
+ *   isum[r][c] = sum_{j < P} icols[idx(b, j)][c],   fsum[r][c] = sum_{j < P} fcols[idx(b, j)][c],
+ *   idx(b, j) = node(u(seed, b, j), P)  -- the draw of the negatives above: slot = replicate, draw = position.
+ * Replicate b is a pure function of (seed, b, tables): not of b0, B, n_groups or timing; two runs are bitwise equal.
+ * Integer sums are exact (the caller keeps |icols| <= 2^32, so they cannot overflow).  An fp64 sum is added in ONE
+ * order: j is cut into segments of 16,384 consecutive draws (a function of P alone); in a segment thread t of 256 adds
+ * the rows of j = start + t, + 256, + 512, ... to its accumulator in that order, from +0.0; the 64 accumulators of a
+ * wavefront are summed by an xor butterfly with partner distances 32, 16, 8, 4, 2, 1; the four wavefronts as
+ * ((w0 + w1) + w2) + w3; the segments in ascending order, from segment 0's sum.  No float atomics.
+ * Limits (LPF_ERR_INVALID otherwise, before any launch): 1 <= P < 2^31, 1 <= B < 2^31, b0 >= 0, 0 <= Ci, Cf <=
+ * LPF_BOOTSTRAP_MAX_COLS, Ci + Cf >= 1, 0 <= n_groups <= 65535 (the number of workgroups; 0: eight per CU).  A table
+ * whose rows are 2, 4 or 8 words and 16-byte aligned is read with 16-byte loads.
+ * ---------------------------------------------------------------------------------------------- */
+#define LPF_BOOTSTRAP_MAX_COLS 8
+#define LPF_BOOTSTRAP_SEGMENT 16384
+/* Bytes of workspace: the per-segment partial sums, B * ceil(P / LPF_BOOTSTRAP_SEGMENT) * (Ci + Cf) * 8, and 0 when P
+ * is one segment (workspace may then be NULL); -1 for arguments outside the limits. */
+int64_t lpf_bootstrap_workspace_bytes(int64_t P, int64_t B, int32_t Ci, int32_t Cf, int32_t n_groups);
+/* workspace: 8-byte aligned, written and read by this call only.  A table with no column may be NULL. */
+int lpf_bootstrap_sums(int64_t P, int64_t B, int64_t b0, uint64_t seed, const int64_t *icols, int32_t Ci,
+                       const double *fcols, int32_t Cf, int64_t *isum, double *fsum, int32_t n_groups,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training step of the pair stage (pair_train.hip): the forward of get_pos_encodings
  * (link_transformer.py:182-211) and LinkAttention.message + PyG softmax + scatter-sum (layers.py:193-224) with the
  * state a backward pass needs, and the gradients torch autograd derives from them (the reference's training step,

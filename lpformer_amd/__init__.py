@@ -28,11 +28,16 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
     negative_rows, negative_pairs       uniform negatives that avoid known edges, drawn on the device: K targets per
                                         source / M distinct pairs; UniformNegatives (fresh non-edges per training step
                                         for train_epoch(negatives=...)), negatives_reference (numpy restatement)
+    bootstrap_metrics, compare_metrics  standard errors, percentile intervals and paired p-values of Hits@K / MRR / AUC by
+                                        a bootstrap over the positives (device resampling kernel); bootstrap_by_bin,
+                                        bootstrap_sums (the building block), bootstrap_sums_reference (numpy restatement)
     link_split                          edge list + features -> a data dict with train / valid / test positives and
                                         edge-aware negatives, ready for fit and evaluate_model
     graph, data                         CSR containers and the data-dict builder
 """
 from . import evaluate, graph, mask_delta, readers  # noqa: F401
+from .bootstrap import (bootstrap_by_bin, bootstrap_metrics, bootstrap_sums, bootstrap_sums_reference,  # noqa: F401
+                        compare_metrics)
 from .data import link_split  # noqa: F401
 from .distance import DIST_BINS, pair_distance  # noqa: F401
 from .epoch import TrainEdges, fit, train_epoch  # noqa: F401
@@ -59,4 +64,5 @@ __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_
            "TrainEdges", "train_epoch", "fit", "pair_distance", "DIST_BINS", "pair_walks",
            "pair_katz", "katz_from_walks", "walks_reference", "negative_rows", "negative_pairs", "UniformNegatives",
            "negatives_reference", "link_split", "pair_hop_counts", "hop_counts_reference", "elph_features",
-           "ball_jaccard"]
+           "ball_jaccard", "bootstrap_sums", "bootstrap_sums_reference", "bootstrap_metrics", "compare_metrics",
+           "bootstrap_by_bin"]

@@ -2,7 +2,7 @@
 // (lpf_negative_pairs) drawn on the device against a "known" CSR with sorted, unique int32 columns.  Fixed output
 // shapes, one integer counter per call, nothing for the host to read in between.
 //
-// The draw (restated in include/lpformer_hip.h and in lpformer_amd/negatives.py), all in uint64:
+// The draw (draw_common.h; restated in include/lpformer_hip.h and in lpformer_amd/negatives.py), all in uint64:
 //   mix64(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
 //   G = 0x9E3779B97F4A7C15;  key(seed, i) = mix64(seed + G (i + 1));  u(seed, i, j) = mix64(key(seed, i) + G (j + 1))
 //   node(u, n) = (u * n) >> 64
@@ -20,27 +20,14 @@
 //
 // Integers only, no float atomics; the two counters are integer atomics, one per wavefront that has something to add.
 #include "lpf_common.h"
+#include "draw_common.h"
 
 namespace {
 
 constexpr int NS_TABLE = 2048;                  // hash-set slots per row (a power of two)
 constexpr int NS_PAIR_BLOCK = 256;
-constexpr uint64_t NS_G = 0x9E3779B97F4A7C15ull;
 
 typedef unsigned long long ns_u64;
-
-__device__ __forceinline__ uint64_t ns_mix64(uint64_t z) {
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-__device__ __forceinline__ uint64_t ns_key(uint64_t seed, uint64_t slot) { return ns_mix64(seed + NS_G * (slot + 1)); }
-__device__ __forceinline__ int32_t ns_node(uint64_t key, uint64_t j, uint64_t n) {
-    return (int32_t)__umul64hi(ns_mix64(key + NS_G * (j + 1)), n);
-}
 static_assert(NS_TABLE == 2048, "lpf_hash11 yields 11 bits");
 
 struct RowArgs {
@@ -77,12 +64,12 @@ __global__ __launch_bounds__(LPF_WAVE) void negative_rows_kernel(RowArgs A) {
     int64_t avail = A.n - (r1 - r0) - (lpf_sorted_has(A.col, r0, r1, (int32_t)s) ? 0 : 1);
     avail = avail < 0 ? 0 : avail;
     const int32_t want = avail < K ? (int32_t)avail : K;
-    const uint64_t key = ns_key(A.seed, A.row_base + (uint64_t)r);
+    const uint64_t key = lpf_draw_key(A.seed, A.row_base + (uint64_t)r);
     const uint32_t max_draws = (uint32_t)A.max_draws;
     int32_t kept = 0;
     for (uint32_t j0 = 0; kept < want && j0 < max_draws; j0 += LPF_WAVE) {   // workgroup-uniform
         const uint32_t j = j0 + lane;
-        const int32_t c = ns_node(key, j, (uint64_t)A.n);
+        const int32_t c = lpf_draw_node(key, j, (uint64_t)A.n);
         const bool valid = j < max_draws && c != (int32_t)s && !lpf_sorted_has(A.col, r0, r1, c);
         uint32_t slot = 0;
         if (valid) {
@@ -124,13 +111,13 @@ __global__ __launch_bounds__(NS_PAIR_BLOCK) void negative_pairs_kernel(PairArgs 
     const int64_t i = (int64_t)blockIdx.x * NS_PAIR_BLOCK + threadIdx.x;
     bool lost = false;
     if (i < A.M && (!A.active || A.active[i])) {
-        const uint64_t key = ns_key(A.seed, A.slot_base + (uint64_t)i);
+        const uint64_t key = lpf_draw_key(A.seed, A.slot_base + (uint64_t)i);
         const uint64_t n = (uint64_t)A.n;
         int32_t j = A.next[i];
         j = j < 0 ? 0 : j;
         int64_t a = -1, b = -1;
         for (; j < A.max_draws; ++j) {
-            const int32_t ca = ns_node(key, 2ull * (uint64_t)j, n), cb = ns_node(key, 2ull * (uint64_t)j + 1, n);
+            const int32_t ca = lpf_draw_node(key, 2ull * (uint64_t)j, n), cb = lpf_draw_node(key, 2ull * (uint64_t)j + 1, n);
             if (ca == cb) continue;
             if (lpf_sorted_has(A.col, A.rowptr[ca], A.rowptr[ca + 1], cb)) continue;
             if (lpf_sorted_has(A.col, A.rowptr[cb], A.rowptr[cb + 1], ca)) continue;
