@@ -359,8 +359,16 @@ int lpf_select_export(int64_t bs, const int32_t *type_ptr, const void *entries, 
  * Host-prepared, parameter-only tables (lpformer_amd/fold.py builds them in float64, stores fp32):
  *   pe_tab   float[3][D][4]  per type t and hidden unit k: (g_k (w0_k - mean w0), g_k (w1_k - mean w1),
  *                            g_k (b_k - mean b), beta_k) -- first PE Linear with the LayerNorm centring folded in
- *   pe_stat  float[3][8]     centred second moments over k of (w0, w1, b): C00, C11, Cbb, C01, C0b, C1b, 0, 0
- *                            (LayerNorm variance of W1 [x,y] + b1 as a quadratic form in (x, y))
+ *   pe_stat  float[6][8]     rows 0-2, per type: centred second moments over k of (w0, w1, b): C00, C11, Cbb, C01, C0b,
+ *                            C1b, 0, c  (the LayerNorm variance of W1 [x,y] + b1 as a quadratic form in (x, y); the
+ *                            statement of the form for host-side restatements, not read on the device);
+ *                            rows 3-5, per type: l00, l10, l20, l11, l21, l22, 0, c: the lower-triangular factor L of
+ *                            that moment matrix M = L L^T.  The kernels read these rows and take the variance as the
+ *                            sum of squares (l00 x + l10 y + l20)^2 + (l11 y + l21)^2 + l22^2 (the quadratic form of M
+ *                            written out cancels where w1 ~ -w0 and x ~ y); slot 7: the no-flip radius c of the
+ *                            pair-major kernels (fold.no_flip_radius), unused elsewhere.
+ *                            The table had rows 0-2 only before, which the kernels read; signatures are unchanged, and
+ *                            the table is always made by fold.pe_tables of the package the library ships with.
  *   wfold_packed float[3][D/32][D/8][64][4]: element (t, c, sq, lane, u) = Wfold_t[32c + (lane&31)]
  *                            [(lane>>5)*(D/2) + 4 sq + u]  with Wfold_t = W_r[:, D:] W2_t  (MFMA A-operand order)
  *   bfold    float[3][D] = W_r[:, D:] (2 b2_t) ;  att float[D]

@@ -35,9 +35,7 @@ __device__ __forceinline__ void pair_scores_tile(
     const float pa = valid ? sel_pa[e] : 0.f, pb = valid ? sel_pb[e] : 0.f;
     const int32_t node = valid ? sel_node[e] : 0, pr = valid ? sel_pair[e] : 0;
 
-    PeStat st;
-    st.c00 = pe_stat[8 * t + 0]; st.c11 = pe_stat[8 * t + 1]; st.cbb = pe_stat[8 * t + 2];
-    st.c01 = pe_stat[8 * t + 3]; st.c0b = pe_stat[8 * t + 4]; st.c1b = pe_stat[8 * t + 5];
+    const PeStat st = pe_load_stat(pe_stat, t);
     const float r_ab = pe_rstd(st, pa, pb), r_ba = pe_rstd(st, pb, pa);
 
     f32x16 acc[NT];
@@ -298,9 +296,7 @@ __global__ __launch_bounds__(256) void pair_softmax_gather_kernel(
             acch[t] = make_float4(0.f, 0.f, 0.f, 0.f);
             asum[t] = 0.f;
             if (cnt[t] == 0) continue;
-            PeStat st;
-            st.c00 = pe_stat[8 * t + 0]; st.c11 = pe_stat[8 * t + 1]; st.cbb = pe_stat[8 * t + 2];
-            st.c01 = pe_stat[8 * t + 3]; st.c0b = pe_stat[8 * t + 4]; st.c1b = pe_stat[8 * t + 5];
+            const PeStat st = pe_load_stat(pe_stat, t);
             float4 k[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u)
@@ -385,9 +381,7 @@ __global__ __launch_bounds__(256) void pair_softmax_gather_heavy_kernel(
         acch[t] = make_float4(0.f, 0.f, 0.f, 0.f);
         asum[t] = 0.f;
         if (cnt[t] == 0) continue;
-        PeStat st;
-        st.c00 = pe_stat[8 * t + 0]; st.c11 = pe_stat[8 * t + 1]; st.cbb = pe_stat[8 * t + 2];
-        st.c01 = pe_stat[8 * t + 3]; st.c0b = pe_stat[8 * t + 4]; st.c1b = pe_stat[8 * t + 5];
+        const PeStat st = pe_load_stat(pe_stat, t);
         float4 k[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u)

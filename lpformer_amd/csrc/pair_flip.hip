@@ -37,7 +37,7 @@ struct FlipArgs {
     const float *Z; uint32_t ldz;   // (ZB: bf16 rows, ldz in bf16 elements)
     const float *q; uint32_t ldq;
     const float *pe_tab;       // [3][D][4]   (ta, tc, td, beta) per hidden unit, times +1 (unit in S0) or -1
-    const float *pe_stat;      // [3][8]
+    const float *pe_stat;      // [6][8]
     const float *base;         // [3][4][D]   P0, Q0, R0, C0 = 2 B0 + bfold
     const float *wfoldT;       // [3][D][D]   wfoldT[t][k][c] = Wfold_t[c][k]
     const float *att;          // [D]
@@ -48,8 +48,7 @@ struct FlipArgs {
 
 // 1 / sqrt(var + eps) of the hidden layer's LayerNorm (closed form, pe_common.h) with the hardware reciprocal square root
 __device__ __forceinline__ float fl_rstd(const PeStat &s, float x, float y) {
-    const float var = s.c00 * x * x + s.c11 * y * y + s.cbb + 2.0f * (s.c01 * x * y + s.c0b * x + s.c1b * y);
-    return __builtin_amdgcn_rsqf(fmaxf(var, 0.0f) + 1e-5f);
+    return __builtin_amdgcn_rsqf(pe_var(s.l00, s.l10, s.l20, s.l11, s.l21, s.l22, x, y) + 1e-5f);
 }
 
 // G = D/4 lanes per entry; NTH threads per workgroup; WTL = how many types keep their Wfold^T in LDS (1: the one-hop

@@ -60,7 +60,7 @@ struct RowsArgs {
     const float *Z; uint32_t ldz;   // (ZB: bf16 rows, ldz in bf16 elements)
     const float *q; uint32_t ldq;
     const float *pe_tab;       // [3][D][4]   (ta, tc, td, beta) per hidden unit, times +1 (unit in S0) or -1
-    const float *pe_stat;      // [3][8]
+    const float *pe_stat;      // [6][8]: rows 3-5, the factor rows, are read (pe_common.h)
     const float *base;         // [3][4][D]   P0, Q0, R0, C0 = 2 B0 + bfold
     const float *wfoldT;       // [3][D][D]   wfoldT[t][k][c] = Wfold_t[c][k]
     const float *att;          // [D]
@@ -118,7 +118,7 @@ template <int G, int NTH, int WTL, bool PT = false, int NV = 1>
 struct PrLds {
     static constexpr int GG = G * NV, D = 4 * GG, NG = (NTH / 64) * (64 / G), NP = pr_patterns(GG, PT);
     static constexpr int TAB = 0, BASE = TAB + 3 * D, VEC = BASE + 3 * NP * D, CONST_ROW = VEC + 3 * GG, STAT = CONST_ROW + GG;
-    static constexpr int WT = STAT + 6;                      // (pe_stat: 3 x 8 floats)
+    static constexpr int WT = STAT + 6;                      // (pe_stat: its 3 factor rows of 8 floats)
     static constexpr int REC = WT + (PT ? 0 : WTL) * D * GG; // int4 [NG][16]
     static constexpr int SC = REC + NG * 16;                 // f32x2 [NG][16]  (NG * 8 float4)
     static constexpr int META = SC + NG * 8;                 // int [NG][16]    (NG * 4 float4)
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
     float4 *const lbase = pr_lds + L::BASE;      // [3][NP][4][GG]
     float4 *const lvec = pr_lds + L::VEC;        // [3][GG]: att_bias, ln_g, ln_b by feature quad
     float4 *const lconst = pr_lds + L::CONST_ROW;   // [GG]: the row of a pair without entries
-    float *const lstat = reinterpret_cast<float *>(pr_lds + L::STAT);   // [3][8]
+    float *const lstat = reinterpret_cast<float *>(pr_lds + L::STAT);   // [3][8]: the factor rows
     float4 *const lwt = pr_lds + L::WT;          // [WTL][D][GG]
     int4 *const lrec = reinterpret_cast<int4 *>(pr_lds + L::REC);
     f32x2 *const lsc = reinterpret_cast<f32x2 *>(pr_lds + L::SC);
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
                 tv[u] = *reinterpret_cast<const float4 *>(src + 4 * (i % GG));
             }
         }
-        const float ts = ft < 24 ? A.pe_stat[ft] : 0.f;
+        const float ts = ft < 24 ? A.pe_stat[PE_STAT_FACTOR + ft] : 0.f;
 #pragma unroll
         for (int u = 0; u < N3; ++u) {
             const int i = u * FT + ft;
@@ -700,7 +700,7 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
                            ((head || more) ? 16 : 0) | (head ? 32 : 0) | 64 | ((head && !more && inl) ? 128 : 0);
                     const float *st = lstat + 8 * t;
                     const float pa = __int_as_float(rec.z), pb = __int_as_float(rec.w);
-                    // pe_stat[t][7]: inside [0, c]^2 no hidden unit leaves the pattern of (0, 0), in either argument order
+                    // pe_stat[3 + t][7]: inside [0, c]^2 no hidden unit leaves the pattern of (0, 0), in either argument order
                     // (fold.no_flip_radius): such an entry needs no look at its units at all
                     if constexpr (PT) {
                         // bits 9-14 / 15-20: row t * NP + s of the pattern table for (pa, pb) / (pb, pa).  Outside the
@@ -721,9 +721,9 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
                     } else {
                         if (!(fmaxf(pa, pb) <= st[7])) meta |= 256;
                     }
-                    const float vab = st[0] * pa * pa + st[1] * pb * pb + st[2] + 2.0f * (st[3] * pa * pb + st[4] * pa + st[5] * pb);
-                    const float vba = st[0] * pb * pb + st[1] * pa * pa + st[2] + 2.0f * (st[3] * pa * pb + st[4] * pb + st[5] * pa);
-                    sc = f32x2{__builtin_amdgcn_rsqf(fmaxf(vab, 0.0f) + 1e-5f), __builtin_amdgcn_rsqf(fmaxf(vba, 0.0f) + 1e-5f)};
+                    const float vab = pe_var(st[0], st[1], st[2], st[3], st[4], st[5], pa, pb);
+                    const float vba = pe_var(st[0], st[1], st[2], st[3], st[4], st[5], pb, pa);
+                    sc = f32x2{__builtin_amdgcn_rsqf(vab + 1e-5f), __builtin_amdgcn_rsqf(vba + 1e-5f)};
                 }
                 lr[i] = rec;
                 lm[i] = meta;

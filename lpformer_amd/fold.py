@@ -13,8 +13,13 @@ Writing W_r = [W_rx | W_rp] this is   k_e = Z[v_e] + Wfold_t h_e + bfold_t   wit
     Wfold_t = W_rp W2_t ,  bfold_t = W_rp (2 b2_t)
 
 and LN_t of the 2-input first layer has closed-form statistics: with u_k = w0_k x + w1_k y + b_k,
-mean_k u = m0 x + m1 y + mb and var_k u is the quadratic form of the centred second moments of (w0, w1, b).
-The tables below carry exactly those quantities (layouts documented in include/lpformer_hip.h).
+mean_k u = m0 x + m1 y + mb and var_k u is the quadratic form (x, y, 1) M (x, y, 1)^T of the centred second moments M of
+(w0, w1, b).  The tables below carry those quantities (layouts documented in include/lpformer_hip.h) -- M twice: its six
+entries (rows 0-2 of ``pe_stat``: the statement of the form, which host-side restatements read) and its factor L,
+M = L L^T (rows 3-5), from which the kernels evaluate the variance as the sum of squares |L^T (x, y, 1)|^2
+(``pe_variance``): written out in the six moments it is a difference of large terms where the layer has learned pa - pb
+(w1 ~ -w0) and pa ~ pb, and fp32 storage and arithmetic then lose u kappa, kappa = (sum of the terms' magnitudes) / var
+~ 1e4; the sum of squares loses u sqrt(kappa).
 """
 from __future__ import annotations
 
@@ -27,10 +32,22 @@ def _f64(t):
     return t.detach().cpu().double().numpy()
 
 
+def pe_variance(st, x, y):
+    """var_k(w0_k x + w1_k y + b_k) from a factor row ``st`` = (l00, l10, l20, l11, l21, l22, ...) of ``pe_stat`` (rows
+    3-5): the sum of squares |L^T (x, y, 1)|^2 (numpy arrays or torch tensors alike; never negative)."""
+    a = st[0] * x + st[1] * y + st[2]
+    b = st[3] * y + st[4]
+    return a * a + b * b + st[5] * st[5]
+
+
 def pe_tables(state: dict, dim: int, n_types: int):
-    """pe_tab float32[3, D, 4], pe_stat float32[3, 8] from the ``ppr_encoder_*`` MLP parameters."""
+    """pe_tab float32[3, D, 4], pe_stat float32[6, 8] from the ``ppr_encoder_*`` MLP parameters.  pe_stat[t, :6] =
+    (C00, C11, Cbb, C01, C0b, C1b), the centred second moments of (w0, w1, b) of type t;  pe_stat[3 + t, :6] =
+    (l00, l10, l20, l11, l21, l22), the lower-triangular factor of that moment matrix, which is what the kernels read:
+    L^T is the triangular factor of a QR decomposition of the centred columns / sqrt(D), in float64 -- it is not taken
+    from the moment matrix, so a (near-)singular one (w1 = -w0) needs no special case."""
     tab = np.zeros((3, dim, 4), np.float64)
-    stat = np.zeros((3, 8), np.float64)
+    stat = np.zeros((6, 8), np.float64)
     for t in range(n_types):
         k = PE_KEYS[t]
         w1, b1 = _f64(state[f"{k}.linears.0.weight"]), _f64(state[f"{k}.linears.0.bias"])  # [D,2], [D]
@@ -39,6 +56,8 @@ def pe_tables(state: dict, dim: int, n_types: int):
         tab[t, :, 0], tab[t, :, 1], tab[t, :, 2], tab[t, :, 3] = g * w0c, g * w1c, g * bc, be
         stat[t, :6] = [(w0c * w0c).mean(), (w1c * w1c).mean(), (bc * bc).mean(), (w0c * w1c).mean(),
                        (w0c * bc).mean(), (w1c * bc).mean()]
+        r = np.linalg.qr(np.stack([w0c, w1c, bc], axis=1) / np.sqrt(dim), mode="r")     # M = R^T R, L = R^T
+        stat[3 + t, :6] = [r[0, 0], r[0, 1], r[0, 2], r[1, 1], r[1, 2], r[2, 2]]
     return tab.astype(np.float32), stat.astype(np.float32)
 
 
@@ -79,7 +98,8 @@ def flip_tables(state: dict, dim: int, n_types: int, prefix="att_layers.0.att"):
     return tabs.astype(np.float32), base.astype(np.float32), s0, np.ascontiguousarray(wt.astype(np.float32))
 
 
-def no_flip_radius(tab_signed: np.ndarray, stat: np.ndarray, grid: int = 41, c_max: float = 0.5) -> float:
+def no_flip_radius(tab_signed: np.ndarray, stat: np.ndarray, grid: int = 41, c_max: float = 0.5,
+                   factor: bool = False) -> float:
     """Largest c (bisection to 1e-4, then shrunk by 5 %) such that on [0, c]^2 NO hidden unit of one PE MLP leaves the
     pattern of (0, 0): z_k(x, y) = r(x, y) (ta_k x + tc_k y + td_k) + beta_k > 0 for every unit k of ``tab_signed`` [D, 4]
     (``flip_tables``: signed for that pattern) on a ``grid`` x ``grid`` lattice of the square, float64.  The square is
@@ -87,13 +107,17 @@ def no_flip_radius(tab_signed: np.ndarray, stat: np.ndarray, grid: int = 41, c_m
     attention kernel (csrc/pair_rows.hip) then takes the base vectors as they are and never looks at the entry's units.
     (Between lattice points z moves by O((c / grid)^2) of its curvature -- a unit that dips below zero there does so by
     ~1e-7 and owes a correction of that size, far below the fp32 noise of the sums it would join.)  0 when some unit is
-    already at or below zero at the origin."""
+    already at or below zero at the origin.  ``stat``: the type's row of ``pe_stat`` -- its six moments, or with
+    ``factor`` its factor row (3 + t), the variance the kernels evaluate and the one ``LinkTransformer`` decides by."""
     tab, st = np.asarray(tab_signed, np.float64), np.asarray(stat, np.float64)
 
     def ok(c):
         g = np.linspace(0.0, c, grid)
         xx, yy = (a.ravel() for a in np.meshgrid(g, g, indexing="ij"))
-        var = st[0] * xx * xx + st[1] * yy * yy + st[2] + 2.0 * (st[3] * xx * yy + st[4] * xx + st[5] * yy)
+        if factor:
+            var = pe_variance(st, xx, yy)
+        else:
+            var = st[0] * xx * xx + st[1] * yy * yy + st[2] + 2.0 * (st[3] * xx * yy + st[4] * xx + st[5] * yy)
         r = 1.0 / np.sqrt(np.maximum(var, 0.0) + 1e-5)
         z = r[:, None] * (xx[:, None] * tab[:, 0] + yy[:, None] * tab[:, 1] + tab[:, 2]) + tab[:, 3]
         return bool(z.min() > 0.0)

@@ -677,11 +677,13 @@ class LinkTransformer(nn.Module):
         out = fold.fold_attention(sd, self.dim, self.n_types)
         out["pe_tab"], out["pe_stat"] = fold.pe_tables(sd, self.dim, self.n_types)
         out["flip_tab"], out["flip_base"], _, out["wfold_t"] = fold.flip_tables(sd, self.dim, self.n_types)
-        # pe_stat[t][7]: the square of PPR value pairs inside which no unit flips (the pair-major kernel skips the look at
-        # an entry's units there; the unit-major kernels never read the slot)
+        # pe_stat[3 + t][7]: the square of PPR value pairs inside which no unit flips (the pair-major kernel skips the look
+        # at an entry's units there; the unit-major kernels never read the slot), decided with the variance the kernels
+        # evaluate (the factor row); row t repeats it next to the moments
         out["pe_stat"] = out["pe_stat"].copy()
         for t in range(self.n_types):
-            out["pe_stat"][t, 7] = fold.no_flip_radius(out["flip_tab"][t], out["pe_stat"][t])
+            out["pe_stat"][3 + t, 7] = fold.no_flip_radius(out["flip_tab"][t], out["pe_stat"][3 + t], factor=True)
+            out["pe_stat"][t, 7] = out["pe_stat"][3 + t, 7]
         dev = {k: torch.from_numpy(np.ascontiguousarray(v)).to(self.device) for k, v in out.items()}
         self._folded = (key, dev)
         self._refolds += 1
@@ -1488,7 +1490,7 @@ class LinkTransformer(nn.Module):
                 total += pa.numel()
                 if pa.numel() == 0:
                     continue
-                tab, st = w["flip_tab"][t], w["pe_stat"][t]     # rows (ta, tc, td, beta) times the unit's sign at (0, 0)
+                tab, st = w["flip_tab"][t], w["pe_stat"][3 + t]     # rows (ta, tc, td, beta) times the unit's sign at (0, 0)
                 slow, named = None, (None, None)
                 if pt is not None:
                     # entries outside the no-flip square whose cells are flagged: the exact path, which starts from the
@@ -1502,8 +1504,7 @@ class LinkTransformer(nn.Module):
                     bits = lambda ids: ((sgn[ids & 31][:, :, None] >> sh) & 1).reshape(ids.numel(), -1)[:, :self.dim].bool()
                     named = (bits(g1), bits(g2))
                 for (x, y), ref in zip(((pa, pb), (pb, pa)), named):
-                    var = st[0] * x * x + st[1] * y * y + st[2] + 2.0 * (st[3] * x * y + st[4] * x + st[5] * y)
-                    r = torch.rsqrt(var.clamp_min(0.0) + 1e-5)
+                    r = torch.rsqrt(fold.pe_variance(st, x, y) + 1e-5)
                     z = r[:, None] * (x[:, None] * tab[:, 0] + y[:, None] * tab[:, 1] + tab[:, 2]) + tab[:, 3]
                     raw += float((z < 0).sum().item())
                     if slow is None:

@@ -115,14 +115,19 @@ def row_floor(x, k: int):
 
 
 # ------------------------------------------------------------------------------------------------- attention
-def pe_hidden(tab, stat, pa, pb):
+def pe_hidden(tab, stat, pa, pb, factor=False):
     """h = ReLU(LN(W1 [pa,pb] + b1)) + ReLU(LN(W1 [pb,pa] + b1)) from ``fold.pe_tables``' rows of one type: [E, D],
-    and the magnitude of its terms (the scale of its fp32 error)."""
+    and the magnitude of its terms (the scale of its fp32 error).  ``stat``: the type's six moments (row t of
+    ``pe_stat``), or with ``factor`` its factor row (3 + t) and the variance as the sum of squares."""
     tab, st = _f64(tab), _f64(stat)
     pa, pb = _f64(pa)[:, None], _f64(pb)[:, None]
 
     def half(x, y):
-        var = st[0] * x * x + st[1] * y * y + st[2] + 2.0 * (st[3] * x * y + st[4] * x + st[5] * y)
+        if factor:
+            a, b = st[0] * x + st[1] * y + st[2], st[3] * y + st[4]
+            var = a * a + b * b + st[5] * st[5]
+        else:
+            var = st[0] * x * x + st[1] * y * y + st[2] + 2.0 * (st[3] * x * y + st[4] * x + st[5] * y)
         r = 1.0 / np.sqrt(np.maximum(var, 0.0) + LN_EPS)
         u = tab[:, 0] * x + tab[:, 1] * y + tab[:, 2]
         return np.maximum(r * u + tab[:, 3], 0.0), np.abs(r * u) + np.abs(tab[:, 3])

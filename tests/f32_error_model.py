@@ -53,6 +53,9 @@ family, see tests/test_gpu_f32_reference.py):
   encoder            per layer C_enc u (|A_hat| |X| |W|^T + |b|) added before the layer's LayerNorm and carried with
                      ln_bound as ``encoder_ref`` carries its dx, + C_enc u max(1, |out|) for the final LayerNorm.
 
+Against the model as defined (tests/unfolded_reference.py: no fold table) the bound gains one term, the conditioning of
+the closed-form LayerNorm of the PE hidden layer: see "conditioning of h_e" below (``unfolded_bounds``).
+
 ``drop_effect`` is the closed form behind the lost-entry near-miss: without entry e the softmax of the remaining
 entries is alpha_f / (1 - alpha_e), so  out' - out = (out - alpha_e k_e) / (1 - alpha_e) - out
 = alpha_e / (1 - alpha_e) (out - k_e)  (the 1e-16 in the denominator aside).
@@ -197,11 +200,142 @@ def encoder_bound(x, rowptr, col, val, layers, *, residual, relu, final_ln, **kw
     return res["out"], res["d_out"] + EPS23 * np.maximum(1.0, np.abs(res["out"]))
 
 
+# ------------------------------------------------------------------------------------------------- conditioning of h_e
+# The kernels evaluate the LayerNorm of the PE hidden layer from the closed form of its variance, the form
+# (x, y, 1) M (x, y, 1)^T of the centred second moments M, held as fp32.  Its conditioning is kappa_e = (sum of the
+# magnitudes of the form's six terms) / (var + eps), tests/unfolded_reference.py.  Written out in M's entries the form
+# carries a RELATIVE error u kappa_e where its terms cancel (storage and arithmetic alike); as the sum of squares
+# |L^T (x, y, 1)|^2 of M's triangular factor, which fold.pe_tables stores next to the moments and the kernels evaluate,
+# u sqrt(kappa_e).
+# r = 1 / sqrt(var + eps) takes half of it, and the element y = r u + beta of h_e an absolute error
+#     b_h[e] = u (sqrt(kappa_e) |r u| + m_e) + u |beta|       per argument order, summed over the two orders,
+# m_e >= |r u| the sum of the magnitudes of the three terms of r u (u (1 + sqrt(kappa_e)) |r u| + u |beta| where they do
+# not cancel; where the first layer has learned pa - pb they cancel at the same entries at which the variance does, and
+# m_e ~ sqrt(kappa_e) |r u| there).  K_e's term |Wfold_t| |h_e| (an h_e good to u |h|) does not hold this.  It reaches
+# the key through |Wfold_t| and goes from there through the same carry as K_e (b_pre, b_post, then the tail), with a
+# constant of its own, C_H[D]:    |got - ref| <= C_ATT b_post + C_H b_post_h.
+# ``kappa="full"`` is the bound of the written-out form (u kappa_e |r u|): what the kernels were good to before.
+# Everything below starts from the state dict in fp64 (|Wfold_t| = |W_rp W2_t|): the bound reads no fold table.
+PE_KEYS = ("ppr_encoder_cn", "ppr_encoder_onehop", "ppr_encoder_non1hop")
+
+
+def fold64(msd, dim):
+    """wfold [3, D, D] = W_rp W2_t, bfold [3, D] = W_rp (2 b2_t) and att in fp64 from the fp64 state dict ``msd``."""
+    w_rp = msd["att_layers.0.att.lin_r.weight"][:, dim:]
+    wfold, bfold = np.zeros((3, dim, dim)), np.zeros((3, dim))
+    for t, k in enumerate(PE_KEYS):
+        if f"{k}.linears.1.weight" in msd:
+            wfold[t] = w_rp @ msd[f"{k}.linears.1.weight"]
+            bfold[t] = w_rp @ (2.0 * msd[f"{k}.linears.1.bias"])
+    return {"wfold": wfold, "bfold": bfold, "att": msd["att_layers.0.att.att"].reshape(-1)}
+
+
+def tail_fold64(msd, ssd, dim):
+    """The tables ``tail_bound`` / ``tail_sigma`` take, folded in fp64 from the state dicts (for the BOUND only: the
+    unfolded reference computes its logits layer by layer)."""
+    we1, be1 = msd["elementwise_lin.linears.1.weight"], msd["elementwise_lin.linears.1.bias"]
+    wp1, bp1 = msd["pairwise_lin.linears.1.weight"], msd["pairwise_lin.linears.1.bias"]
+    ws0, bs0 = ssd["lins.0.weight"], ssd["lins.0.bias"]
+    a = np.concatenate([ws0[:, :dim] @ we1, ws0[:, dim:] @ wp1], axis=1)
+    return {"w_p0": msd["pairwise_lin.linears.0.weight"], "b_p0": msd["pairwise_lin.linears.0.bias"],
+            "lnB_g": msd["pairwise_lin.norm.weight"], "lnB_b": msd["pairwise_lin.norm.bias"], "A": a,
+            "c": bs0 + ws0[:, :dim] @ be1 + ws0[:, dim:] @ bp1, "w_dot": ssd["lins.1.weight"].reshape(-1),
+            "b_dot": ssd["lins.1.bias"]}
+
+
+def h_bound(ent, msd, kappa="root"):
+    """b_h [E, D] with C_H = 1.  ``kappa``: "root" -- u (sqrt(kappa) |r u| + m) + u |beta| (the variance as a sum of
+    squares);  "full" -- kappa in its place (the six moments written out);  "none" -- kappa dropped and m = |r u| (an h_e good
+    to u |h_e|: the near-miss of a model without the term)."""
+    kap = {"full": ent["kappa"], "root": np.sqrt(ent["kappa"]), "none": np.ones_like(ent["kappa"])}[kappa]
+    rm0, rm1 = (ent["ru0"], ent["ru1"]) if kappa == "none" else (ent["rm0"], ent["rm1"])
+    beta = np.zeros((3, ent["h"].shape[1]))
+    for t, k in enumerate(PE_KEYS):
+        if f"{k}.norm.bias" in msd:
+            beta[t] = np.abs(msd[f"{k}.norm.bias"])
+    return EPS23 * (kap[:, :1] * ent["ru0"] + rm0 + kap[:, 1:] * ent["ru1"] + rm1 + 2.0 * beta[ent["type"]])
+
+
+def conditioning_bound(ref, w, qmag, att_bias, ln_g, ln_b, b_h):
+    """(b_pre_h, b_post_h) [bs, D]: the key error |Wfold_t| b_h carried like K_e in ``attention_bound`` (C_H = 1)."""
+    pre = ref["pre"]
+    ent = ref["ent"]
+    acc, sens2 = np.zeros_like(pre), np.zeros_like(pre)
+    if ent is not None:
+        pair, tt = ent["pair"], ent["type"]
+        dk = np.zeros_like(b_h)
+        for t in range(3):
+            m = tt == t
+            if m.any():
+                dk[m] = b_h[m] @ np.abs(w["wfold"][t]).T
+        terms = np.abs(w["att"] * qmag[pair]) * dk
+        ds = np.sqrt((terms * terms).sum(axis=1))
+        dev = np.abs(ent["k"] - (pre - _f64(att_bias))[pair])
+        np.add.at(acc, pair, ent["alpha"][:, None] * dk)
+        np.add.at(sens2, pair, (ent["alpha"][:, None] * dev * ds[:, None]) ** 2)
+    _, xhat, sd = R.layer_norm(pre, _f64(ln_g), _f64(ln_b))
+    b_pre = acc + np.sqrt(sens2)
+    return b_pre, R.ln_bound(b_pre, xhat, sd, _f64(ln_g))
+
+
+def unfolded_bounds(ref, x_node, batch, msd, ssd, kappa="root"):
+    """Every C = 1 piece of the bounds of one unfolded reference (``unfolded_reference.scoring``), from the state dicts:
+    ``b_post`` (``attention_bound``; Z and q are not taken from a device here, so their D-term fp32 products are charged
+    too: |Z| and |q| enter with their quadrature magnitudes sqrt(x^2 (W^2)^T + b^2) added), ``b_post_h`` (above),
+    ``b_re``, the tail's tables and the tail's own share ``s_own`` of the logit's scale."""
+    x, batch = _f64(x_node), np.asarray(batch, np.int64)
+    d = x.shape[1]
+    w = fold64(msd, d)
+    w_r, b_r = msd["att_layers.0.att.lin_r.weight"], msd["att_layers.0.att.lin_r.bias"]
+    w_l, b_l = msd["att_layers.0.att.lin_l.weight"], msd["att_layers.0.att.lin_l.bias"]
+    bias = msd["att_layers.0.att.bias"]
+    ln = (msd["att_layers.0.post_att_norm.weight"], msd["att_layers.0.post_att_norm.bias"])
+    zmag = np.abs(x @ w_r[:, :d].T + b_r) + np.sqrt((x * x) @ (w_r[:, :d] ** 2).T + b_r ** 2)
+    x2 = x[batch[0]] ** 2 + x[batch[1]] ** 2
+    qmag = np.abs(ref["q"]) + np.sqrt(x2 @ (w_l ** 2).T + 2.0 * b_l ** 2)
+    out = attention_bound(ref, zmag, w, qmag, bias, *ln)
+    if ref["ent"] is not None:
+        b_h = h_bound(ref["ent"], msd, kappa)
+    else:
+        b_h = None
+    out["b_pre_h"], out["b_post_h"] = conditioning_bound(ref, w, qmag, bias, *ln, b_h)
+    if ssd is not None:
+        out["tabs"] = tail_fold64(msd, ssd, d)
+        out["b_re"] = elementwise_bound(x, batch, msd["elementwise_lin.linears.0.weight"],
+                                        msd["elementwise_lin.linears.0.bias"], msd["elementwise_lin.norm.weight"],
+                                        msd["elementwise_lin.norm.bias"])
+        out["s_own"] = tail_sigma(ref["post"], ref["feats"], ref["r_e"], out["tabs"], np.zeros_like(ref["post"]),
+                                  out["b_re"])
+    return out
+
+
+def row_bound(bnd, c_att, c_h):
+    return c_att * bnd["b_post"] + c_h * bnd["b_post_h"]
+
+
+def logit_bound(ref, bnd, rows_b, c_tail):
+    """c_tail s_l with the rows at ``rows_b`` (``row_bound``), in quadrature with the tail's own roundings."""
+    s_rows = tail_sigma(ref["post"], ref["feats"], ref["r_e"], bnd["tabs"], rows_b, np.zeros_like(bnd["b_re"]), own=False)
+    return c_tail * np.sqrt(s_rows ** 2 + bnd["s_own"] ** 2)
+
+
+def layer_norm_moments_f32(pre, ln_g, ln_b):
+    """Near-miss: LayerNorm in float32 with the variance taken as E[x^2] - E[x]^2."""
+    f = np.float32
+    x = np.asarray(pre, f)
+    n = f(x.shape[1])
+    mu = x.sum(axis=1, keepdims=True, dtype=f) / n
+    var = (x * x).sum(axis=1, keepdims=True, dtype=f) / n - mu * mu
+    return (x - mu) / np.sqrt(np.maximum(var, f(0)) + f(R.LN_EPS)) * np.asarray(ln_g, f) + np.asarray(ln_b, f)
+
+
 # ------------------------------------------------------------------------------------------------- fp32 evaluation
-def attention_f32(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, shift=True, score_rounder=None):
+def attention_f32(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, shift=True, score_rounder=None, factor=False):
     """The same algebra in plain float32 numpy, entries in order, np.float32 throughout (what the bound is checked
     against on the CPU).  ``shift=False``: the softmax without its maximum shift;  ``score_rounder``: the scores pass
-    through it before the softmax (near-misses that the bound has to reject)."""
+    through it before the softmax (near-misses that the bound has to reject).  The variance is the quadratic form of the
+    six centred second moments (rows 0-2 of ``pe_stat``) written out;  ``factor``: the sum of squares of the moment
+    matrix's triangular factor (rows 3-5), which is what the kernels evaluate."""
     f = np.float32
     z, q = np.asarray(z, f), np.asarray(q, f)
     wfold, bfold, att = (np.asarray(w[k], f) for k in ("wfold", "bfold", "att"))
@@ -213,11 +347,15 @@ def attention_f32(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, shift=True, score_r
             continue
         pair, node = np.asarray(s[0][0], np.int64), np.asarray(s[0][1], np.int64)
         pa, pb = np.asarray(s[1], f)[:, None], np.asarray(s[2], f)[:, None]
-        st = stat[t]
+        st = stat[3 + t] if factor else stat[t]
 
         def half(x, y):
-            var = st[0] * x * x + st[1] * y * y + st[2] + f(2) * (st[3] * x * y + st[4] * x + st[5] * y)
-            r = f(1) / np.sqrt(np.maximum(var, f(0)) + f(R.LN_EPS))
+            if not factor:
+                var = st[0] * x * x + st[1] * y * y + st[2] + f(2) * (st[3] * x * y + st[4] * x + st[5] * y)
+                r = f(1) / np.sqrt(np.maximum(var, f(0)) + f(R.LN_EPS))
+            else:
+                a, b = st[0] * x + st[1] * y + st[2], st[3] * y + st[4]
+                r = f(1) / np.sqrt(a * a + b * b + st[5] * st[5] + f(R.LN_EPS))
             u = tab[t][:, 0] * x + tab[t][:, 1] * y + tab[t][:, 2]
             return np.maximum(r * u + tab[t][:, 3], f(0))
         h = half(pa, pb) + half(pb, pa)

@@ -11,6 +11,7 @@ import lpformer_amd
 from lpformer_amd import _lib
 from lpformer_amd import data as D
 from tests import bf16_reference as R
+from tests import param_regimes
 
 DEV = "cuda:0"
 N_ISO = 20
@@ -55,9 +56,10 @@ def _graph(seed, n=2000, weighted=False):
     return allp[:, u], (None if allw is None else allw[u])
 
 
-def _setup(dim, mode, seed=0, layers=1, residual=False, weighted=False, f_in=40, bs=700, att_gain=1.0):
+def _setup(dim, mode, seed=0, layers=1, residual=False, weighted=False, f_in=40, bs=700, att_gain=1.0, regime=None):
     """``att_gain`` multiplies the attention vector ``att`` in place: scores are linear in it, so every pair's score
-    range is scaled by the gain and nothing else changes."""
+    range is scaled by the gain and nothing else changes.  ``regime``: a rewrite of tests/param_regimes.py applied after
+    the initialisation (None: none)."""
     n = 2000
     ei, w = _graph(seed, n, weighted)
     rng = np.random.default_rng(seed + 1)
@@ -74,6 +76,8 @@ def _setup(dim, mode, seed=0, layers=1, residual=False, weighted=False, f_in=40,
                 p.add_(0.1 * torch.randn_like(p))
         if att_gain != 1.0:
             model.att_layers[0].att.att.mul_(att_gain)
+    if regime is not None:
+        param_regimes.apply(model, score, regime, seed)
     batch = D.sample_pairs(ei, n, bs, seed=seed + 2, frac_edges=0.3)
     iso = np.arange(n - N_ISO, n)
     batch[:, :8] = np.array([[0, 1, 0, 5, 7, 7, 0, iso[0]],
