@@ -11,7 +11,10 @@ import re
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-HIP_LIB_PATH = os.path.join(_HERE, "liblpformer_hip.so")
+INSTALLED_HIP_LIB_PATH = os.path.join(_HERE, "liblpformer_hip.so")
+# LPF_HIP_LIB, read once here: a tuning build of the kernel library (tools/variant.sh) to load instead of the installed
+# one.  Whatever it names is what is loaded -- a missing file is an error, never a reason to take the installed library.
+HIP_LIB_PATH = os.environ.get("LPF_HIP_LIB") or INSTALLED_HIP_LIB_PATH
 HOST_LIB_PATH = os.path.join(_HERE, "liblpformer_host.so")
 
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lpformer_hip.h")
@@ -178,6 +181,9 @@ def hip():
     """The gfx950 kernel library.  Raises if it has not been built (python __graft_entry__.py build)."""
     global _hip
     if _hip is None:
+        if HIP_LIB_PATH != INSTALLED_HIP_LIB_PATH and not os.path.exists(HIP_LIB_PATH):
+            raise LpfError(f"LPF_HIP_LIB names {HIP_LIB_PATH}, which does not exist (tools/variant.sh builds and names "
+                           "tuning libraries); the installed library is not loaded in its place")
         if not os.path.exists(HIP_LIB_PATH):
             raise LpfError(f"{HIP_LIB_PATH} not found: build it with `make -C lpformer_amd/csrc` "
                            "(or __graft_entry__.build()); lpformer_amd has no non-HIP fallback")

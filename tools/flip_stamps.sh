@@ -1,5 +1,5 @@
 #!/bin/bash
+# per-wavefront finish times of pair_flip_kernel: tools/flip_stamps.sh [config] "<extra -D flags>"
+set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
-touch lpformer_amd/csrc/pair_flip.hip
-make -C lpformer_amd/csrc EXTRA="-DFL_STAMPS $2" > /dev/null 2>&1
-LPF_CFG=${1:-collab} timeout 300 python3 tools/flip_stamps.py 2>&1 | tail -2
+LPF_CFG=${1:-collab} tools/variant.sh -t 300 -s pair_flip -x "-DFL_STAMPS $2" -- python3 tools/flip_stamps.py | tail -2

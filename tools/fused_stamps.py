@@ -1,5 +1,5 @@
 """Tuning aid: per-tile phase timing of pair_fused_kernel, first 8 tiles of 512 wavefronts.  Needs a library built with
-the stamps compiled in:  make -C lpformer_amd/csrc clean && make -C lpformer_amd/csrc EXTRA=-DLPF_FUSED_STAMPS"""
+the stamps compiled in:  tools/variant.sh -t 600 -s pair_fused -x -DLPF_FUSED_STAMPS -- python3 tools/fused_stamps.py"""
 import os, sys, ctypes as C
 os.environ["LPF_FUSED_DBG"] = "32"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,7 +23,7 @@ torch.cuda.synchronize()
 buf = np.zeros(4096 * 8, np.int64)
 lib = _lib.hip()
 if not hasattr(lib, "lpf_fused_debug_stamps"):
-    sys.exit("this build has no stamps: rebuild with EXTRA=-DLPF_FUSED_STAMPS")
+    sys.exit("this build has no stamps: run it through tools/variant.sh -s pair_fused -x -DLPF_FUSED_STAMPS")
 lib.lpf_fused_debug_stamps.argtypes = [C.c_void_p, C.c_int64]
 assert lib.lpf_fused_debug_stamps(buf.ctypes.data, buf.size) == 0
 s = buf.reshape(512, 8, 8)[:, :, :6]          # wave, tile, stamp

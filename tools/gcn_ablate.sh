@@ -1,8 +1,8 @@
 #!/bin/bash
 # Tuning aid: ablations of gcn_fused_kernel (GF_NOMFMA: no product, GF_NOGATHER: no neighbour loads)
+set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 for ex in "" "-DGF_NOMFMA" "-DGF_NOGATHER" "$@"; do
-  touch lpformer_amd/csrc/gcn_fused.hip
-  make -C lpformer_amd/csrc EXTRA="$ex" > /dev/null 2>&1 || echo "build failed"
-  echo "[$ex] $(timeout 300 python3 tools/enc_time.py 2>&1 | tail -1)"
+  line=$(tools/variant.sh -t 300 -s gcn_fused -x "$ex" -- python3 tools/enc_time.py | tail -1) || exit $?
+  echo "[$ex] $line"
 done

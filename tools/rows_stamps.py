@@ -1,4 +1,4 @@
-"""Tuning aid: phase marks of pair_rows_kernel (build with EXTRA=-DPR_STAMPS): per wavefront start / set-up done / chunk
+"""Tuning aid: phase marks of pair_rows_kernel (tools/rows_stamps.sh): per wavefront start / set-up done / chunk
 sorted / empties / heavy / light end, rounds walked."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

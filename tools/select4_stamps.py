@@ -1,4 +1,4 @@
-"""Tuning aid: where a block's time goes in select4_kernel (build with EXTRA=-DS4_STAMPS; tools/select4_stamps.sh).
+"""Tuning aid: where a block's time goes in select4_kernel (a -DS4_STAMPS build: tools/select4_stamps.sh).
 Thread 0 of every workgroup leaves the wall clock (100 MHz) at the marks of the kernel."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,4 +1,4 @@
-"""Tuning aid: where an item's time goes in select3_run_kernel (build with EXTRA=-DS3_STAMPS; tools/select_stamps.sh).
+"""Tuning aid: where an item's time goes in select3_run_kernel (a -DS3_STAMPS build: tools/select_stamps.sh).
 Thread 0 of every workgroup accumulates wall-clock ticks (100 MHz) between the marks of the item loop."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,4 +1,4 @@
-"""Tuning aid: phase marks of tail_chain_kernel (build with EXTRA=-DTC_STAMPS): per wavefront start / stage A read /
+"""Tuning aid: phase marks of tail_chain_kernel (tools/tail_stamps.sh): per wavefront start / stage A read /
 stage B k-groups done / LayerNorm B done / stage C r_e k-groups done / r_p k-groups done / end; in the three-launch step
 (model.fuse_step, the default at D = 128 fp32) also stage E done, and the r_e k-groups then come BEFORE the rows read.
 Stage E splits further: its gathered rows arrived (the stamped build waits for them there) / its k-loop done / its
