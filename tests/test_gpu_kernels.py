@@ -321,7 +321,8 @@ def test_device_ppr_indexes_match_host_twins(theta):
 
 def test_gemm_tn_weight_gradient():
     """lpf_gemm_tn_f32: C = A^T B with the reduction over the rows split into chunks (dW of a Linear), against fp64
-    torch; ragged N / K / M, a single row, and an empty input."""
+    torch; ragged N / K / M, a single row, and an empty input.
+    (The chunk, round and group edges and padded lda / ldb / ldc, bit-exact: tests/test_gpu_node_train_kernels.py.)"""
     from lpformer_amd import train
     torch.manual_seed(11)
     for m, n, k in ((100_003, 128, 128), (4097, 132, 260), (1, 7, 5), (300, 1, 1433), (0, 16, 8), (50_001, 64, 64), (9000, 32, 64),
@@ -343,7 +344,8 @@ def test_gemm_tn_weight_gradient():
 
 def test_layernorm_backward_kernel():
     """lpf_layernorm_bwd_f32 (through train.layer_norm) against torch autograd in fp64: dx, dgamma, dbeta; several
-    widths, a single row, many rows."""
+    widths, a single row, many rows.
+    (The ReLU and dropout entries, the workgroup cap and padded leading dimensions: tests/test_gpu_node_train_kernels.py.)"""
     from lpformer_amd import train
     torch.manual_seed(5)
     for m, d in ((70_001, 128), (513, 64), (1, 32), (3000, 256), (200, 132)):
