@@ -1219,6 +1219,33 @@ int lpf_pair_scatter_add_f32(int64_t bs, int32_t D, const int64_t *batch, int64_
                              const float *X, int64_t ldx, const float *dmul, int64_t ldm, const float *dsum,
                              int64_t lds, float *dX, int64_t lddx, void *stream);
 
+/* Nearest nodes by embedding similarity (csrc/similar.hip): for each of the S query rows Q[s] the m rows v of the table
+ * T [n, ldt] with the largest score(s, v) = sum_{k < D} Q[s][k] T[v][k], accumulated in fp32 on the fp32-input MFMA
+ * (the order of k is the kernel's); with q_scale [S] and t_scale [n] (both or neither) the score is
+ * (dot * q_scale[s]) * t_scale[v], two fp32 multiplies in that order.  No [S, n] matrix is ever held.
+ * Rows: 16-byte aligned, ldq % 4 == ldt % 4 == 0, ld >= D; columns D .. ld - 1 are never used as values (NaN allowed).
+ * Eligible: every v in [0, n), except -- only when src_ids [S] is given -- the members of the exclusion row of
+ * src_ids[s] (exc_rowptr int64 [n + 1] / exc_col int32, rows sorted and unique; NULL: none) and, with exclude_self,
+ * src_ids[s] itself.  A src_ids[s] outside [0, n) has no eligible node.
+ * Ranking: the key of lpf_segment_topk_f32 with the node id in place of the position -- (ordered uint32 of the score,
+ * -0.0 -> +0.0, NaN below -inf) << 32 | ~v, descending: ties go to the smaller id, NaN scores rank last.  Row s of
+ * ids / scores [S, m] holds the first counts[s] = min(m, eligible) entries, best first, then -1 / -inf.  A returned
+ * score is the one the key holds: -0.0 reads +0.0, a NaN the canonical quiet NaN.  The result is a pure function of
+ * the inputs: it does not depend on n_ranges, on timing or on the order tiles finish in (no float atomics).
+ * The grid is (source tiles) x (n_ranges node ranges, 1 .. 65535; negative: the library default, about two workgroups
+ * per CU when S is small); a merge launch on the same stream joins the ranges.  workspace:
+ * lpf_similar_workspace_bytes(S, m, n_ranges) bytes of device memory (a negative LPF_ERR_* for bad arguments).
+ * Limits: S, n < 2^31 - 1, n >= 1, 1 <= m <= LPF_SIMILAR_MAX_M, D >= 1 (LPF_ERR_INVALID otherwise); D > 4096 returns
+ * LPF_ERR_UNSUPPORTED.  Both symbols were added within ABI 16: the addition changes no existing symbol, so
+ * LPF_ABI_VERSION stays. */
+#define LPF_SIMILAR_MAX_M 256
+int64_t lpf_similar_workspace_bytes(int64_t S, int32_t m, int32_t n_ranges);
+int lpf_similar_topm_f32(int64_t S, int64_t n, int32_t D, const float *Q, int64_t ldq, const float *T, int64_t ldt,
+                         const float *q_scale, const float *t_scale, const int64_t *src_ids,
+                         const int64_t *exc_rowptr, const int32_t *exc_col, int32_t exclude_self, int32_t m,
+                         int32_t n_ranges, void *workspace, int64_t *ids, float *scores, int64_t *counts,
+                         void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Host side (liblpformer_host.so)
  * ---------------------------------------------------------------------------------------------- */

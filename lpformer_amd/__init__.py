@@ -17,6 +17,9 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
                                         elph_features (the ELPH / BUDDY layout), ball_jaccard, hop_counts_reference
                                         (numpy restatement)
     recommend                           top-K new links per source node (device candidates, scoring, top-K)
+    similar_nodes                       the m nodes nearest to each query by inner product or cosine over the encoder's
+                                        output, the raw features or any table (device matrix-core kernel with the top-m
+                                        kept in LDS: no [S, n] matrix); Similar, similar_reference (numpy restatement)
     explain, explain_from_scores        per-pair attention attribution: top nodes, mass per type, entropy (device
                                         segmented reduction); pairs_of (a recommend result's pairs), attention_profile
     threshold_profile, suggest_thresholds   selected-node counts per pair, type and PPR threshold for a whole grid of
@@ -54,6 +57,7 @@ from .link_transformer import MLP, LinkTransformer, mlp_score  # noqa: F401
 from .ppr import calc_ppr, calc_ppr_gpu, get_ppr, load_or_calc_ppr, ppr_coo  # noqa: F401
 from .pyg_api import LPFormer  # noqa: F401
 from .recommend import Recommendations, recommend  # noqa: F401
+from .similar import Similar, similar_nodes, similar_reference  # noqa: F401
 from .threshold_profile import ThresholdProfile, suggest_thresholds, threshold_profile  # noqa: F401
 
 __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_ppr_gpu", "get_ppr",
@@ -65,4 +69,4 @@ __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_
            "pair_katz", "katz_from_walks", "walks_reference", "negative_rows", "negative_pairs", "UniformNegatives",
            "negatives_reference", "link_split", "pair_hop_counts", "hop_counts_reference", "elph_features",
            "ball_jaccard", "bootstrap_sums", "bootstrap_sums_reference", "bootstrap_metrics", "compare_metrics",
-           "bootstrap_by_bin"]
+           "bootstrap_by_bin", "similar_nodes", "similar_reference", "Similar"]

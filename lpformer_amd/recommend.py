@@ -5,7 +5,8 @@ new links of u are most likely?" meant building the candidate pairs by hand, sco
 top-K.  Here the three steps are one call:
 
 1. candidates on the device (``lpf_rec_candidate_count`` / ``lpf_rec_candidate_fill``, csrc/recommend.hip): u's PPR row
-   or every node, minus the exclusion row (by default the model's own typing adjacency) and u itself;
+   or every node, minus the exclusion row (by default the model's own typing adjacency) and u itself; or the nodes
+   most similar to u (``similar.similar_nodes``, csrc/similar.hip), alone or joined with the PPR row's;
 2. scoring through ``evaluate.score_edges`` (logits) -- no scoring path of its own;
 3. ranking by ``lpf_segment_topk_f32``: by logit, ties to the earlier candidate (the smaller id for the generated
    modes), -0.0 == +0.0, NaN below -inf.
@@ -28,7 +29,8 @@ from .ops import raw_stream
 from .sources import model_graphs, node_ids
 
 MAX_K = _lib.CONST["LPF_TOPK_MAX_K"]
-CANDIDATE_MODES = ("ppr", "all", "2hop")
+MAX_SIMILAR = _lib.CONST["LPF_SIMILAR_MAX_M"]
+CANDIDATE_MODES = ("ppr", "all", "2hop", "similar", "ppr+similar")
 
 
 class Recommendations(NamedTuple):
@@ -56,6 +58,18 @@ def plan_chunks(counts, max_pairs: int) -> List[Tuple[int, int]]:
     if c.size:
         chunks.append((lo, int(c.size)))
     return chunks
+
+
+def _check_similar(n_similar, similar_table, similar_metric):
+    """Argument checks of the ``"similar"`` modes' keywords that need no device."""
+    from . import similar
+    if isinstance(n_similar, bool) or not isinstance(n_similar, (int, np.integer)) or \
+            not 1 <= int(n_similar) <= MAX_SIMILAR:
+        raise ValueError(f"n_similar must be an integer in [1, {MAX_SIMILAR}]; got {n_similar!r}")
+    if similar_metric not in similar.METRICS:
+        raise ValueError(f"similar_metric must be one of {similar.METRICS}; got {similar_metric!r}")
+    if not isinstance(similar_table, str) or similar_table not in similar.TABLES:
+        raise ValueError(f"similar_table must be one of {similar.TABLES}; got {similar_table!r}")
 
 
 def _check_args(sources, k, candidates):
@@ -145,6 +159,59 @@ def twohop_candidates(adj, sources: torch.Tensor, exclude_adj: bool, exclude_sel
     return th.counts, fill
 
 
+def similar_candidates(src: torch.Tensor, sim):
+    """``generate_candidates`` for ``candidates="similar"``: the ids of ``sim`` (a ``similar.Similar`` of the sources
+    ``src``) with the padding dropped, in similarity order."""
+    m = sim.ids.shape[1]
+    slot = torch.arange(m, device=src.device)
+
+    def fill(lo: int, hi: int, total: int) -> torch.Tensor:
+        # entry (s, j) goes to output slot offset[s] + j: the live entries of a row are its first counts[s]
+        cnt = sim.counts[lo:hi]
+        offset = torch.cumsum(cnt, 0) - cnt
+        live = slot[None, :] < cnt[:, None]
+        pos = torch.where(live, offset[:, None] + slot[None, :], total)     # (padding lands in a slot past the end)
+        pairs = torch.empty((2, total + 1), dtype=torch.int64, device=src.device)
+        pairs[0].scatter_(0, pos.reshape(-1), src[lo:hi, None].expand(-1, m).reshape(-1))
+        pairs[1].scatter_(0, pos.reshape(-1), sim.ids[lo:hi].reshape(-1))
+        return pairs[:, :total]
+    return sim.counts, fill
+
+
+def union_candidates(n: int, src: torch.Tensor, ppr, min_ppr: float, exclude, exclude_self: bool, sim,
+                     split_threshold: int = -1):
+    """``generate_candidates`` for ``candidates="ppr+similar"``: per source the distinct ids of its ``"ppr"`` candidates
+    and of ``sim`` (a ``similar.Similar`` made with the same exclusion), ascending.  A similar id is also a PPR
+    candidate exactly when its PPR value passes the ``"ppr"`` test (the exclusion is the same on both sides), so the
+    union's size is known from one ``lpf_csr_lookup_f32`` over the [S, m] ids, before anything is built; ``fill`` sorts
+    the keys (row - lo) * n + v of the PPR candidates and of the similar-only ids.  Returns (int64 [2, S]: the union's
+    counts and the PPR candidates', for the call's one read-back; ``make_fill(PPR counts on the host) -> fill``)."""
+    dev = src.device
+    S, m = sim.ids.shape
+    n_ppr, fill_ppr = generate_candidates(n, src, ppr, min_ppr, exclude, exclude_self, split_threshold)
+    live = sim.ids >= 0
+    val = torch.zeros(S * m, dtype=torch.float32, device=dev)
+    if S:
+        rows = src[:, None].expand(-1, m).reshape(-1).contiguous()
+        cols = sim.ids.clamp_min(0).reshape(-1).contiguous()
+        check(_lib.hip().lpf_csr_lookup_f32(S * m, n, ptr(rows), ptr(cols), ptr(ppr.rowptr), ptr(ppr.col),
+                                            ptr(ppr.val), ptr(val), raw_stream(dev)), "lpf_csr_lookup_f32")
+    val = val.reshape(S, m)
+    only = live & ~((val > 0) & (val >= float(np.float32(min_ppr))))   # similar ids the PPR candidates do not hold
+
+    def make_fill(ppr_host):
+        def fill(lo: int, hi: int, total: int) -> torch.Tensor:
+            tp = int(ppr_host[lo:hi].sum())
+            pp = fill_ppr(lo, hi, tp)
+            row = torch.arange(hi - lo, device=dev)
+            key_p = row.repeat_interleave(n_ppr[lo:hi], output_size=tp) * n + pp[1]
+            key_s = torch.where(only[lo:hi], row[:, None] * n + sim.ids[lo:hi], (hi - lo) * n)   # (others: to the end)
+            key = torch.sort(torch.cat([key_p, key_s.reshape(-1)])).values[:total]
+            return torch.stack([src[lo:hi][torch.div(key, n, rounding_mode="floor")], key % n])
+        return fill
+    return torch.stack([n_ppr + only.sum(1), n_ppr]), make_fill
+
+
 def segment_topk(seg_ptr: torch.Tensor, score: torch.Tensor, cand: torch.Tensor, k: int):
     """(ids int64 [S, k], scores float32 [S, k], counts int64 [S]) of the segments ``seg_ptr`` (int64 [S + 1]) of
     ``score`` (float32) / ``cand`` (int64): the top min(k, len) of each segment by score, ties to the earlier position,
@@ -171,15 +238,22 @@ def segment_topk(seg_ptr: torch.Tensor, score: torch.Tensor, cand: torch.Tensor,
 @torch.no_grad()
 def recommend(model, score_func, sources, k: int = 100, *, candidates="ppr", min_ppr: float = 0.0, exclude="adj",
               exclude_self: bool = True, test_set: bool = False, h=None, batch_size: int = 32768,
-              max_pairs: int = 1 << 24, logits: bool = False, split_threshold: int = -1) -> Recommendations:
+              max_pairs: int = 1 << 24, logits: bool = False, split_threshold: int = -1, n_similar: int = 128,
+              similar_table: str = "embedding", similar_metric: str = "cosine") -> Recommendations:
     """The ``k`` highest-scoring candidates v of every source u in ``sources`` (int [S], host or device; duplicates are
     independent rows).
 
     ``candidates``: ``"2hop"`` -- every v that shares a neighbour with u on the split's typing adjacency (``exclude``
     must then be ``"adj"`` or None; ``split_threshold`` is the two-hop kernel's); ``"ppr"`` -- the entries of u's row of the split's PPR matrix (``data["ppr"]``, ``data["ppr_test"]``
     with ``test_set``) whose fp32 value is > 0 and >= ``min_ppr``; ``"all"`` -- every node; or an int tensor [S, M] of
-    explicit candidates, taken as given (no exclusion, duplicates kept).  ``exclude``: ``"adj"`` (the model's typing
-    adjacency of the split), None, a ``graph.CSR`` or a ``graph.DeviceCSR``; ``exclude_self`` drops v = u.
+    explicit candidates, taken as given (no exclusion, duplicates kept); ``"similar"`` -- the ``n_similar`` (at most
+    ``LPF_SIMILAR_MAX_M``) eligible nodes most similar to u by ``similar_metric`` (``"cosine"`` or ``"dot"``) over
+    ``similar_table`` (``"embedding"``: the ``h`` this call scores with; ``"x"``: the raw features), from
+    ``similar.similar_nodes`` -- these stand in SIMILARITY order, most similar first, so a logit tie goes to the more
+    similar node, not to the smaller id; ``"ppr+similar"`` -- the distinct ids of the ``"ppr"`` and the ``"similar"``
+    candidates, ascending (the PPR candidates' counts ride in the same read-back as the union's).  ``exclude``:
+    ``"adj"`` (the model's typing adjacency of the split), None, a ``graph.CSR`` or a ``graph.DeviceCSR``;
+    ``exclude_self`` drops v = u.
 
     Candidates are scored by ``evaluate.score_edges(..., logits=True)`` (``h`` propagated once when not given), ranked by
     logit with ties to the earlier candidate (the smaller id for the generated modes).  ``scores`` are
@@ -190,6 +264,9 @@ def recommend(model, score_func, sources, k: int = 100, *, candidates="ppr", min
     from . import evaluate
     src, explicit = _check_args(sources, k, candidates)
     k = int(k)
+    similar_mode = explicit is None and candidates in ("similar", "ppr+similar")
+    if similar_mode:
+        _check_similar(n_similar, similar_table, similar_metric)
     if int(max_pairs) < 1 or int(batch_size) < 1:
         raise ValueError("max_pairs and batch_size must be positive")
     if model.training:
@@ -210,7 +287,19 @@ def recommend(model, score_func, sources, k: int = 100, *, candidates="ppr", min
             def fill(lo, hi, total):
                 return torch.stack([src[lo:hi].repeat_interleave(M), cand[lo:hi].reshape(-1)])
         else:
-            if candidates == "2hop":
+            if similar_mode:
+                from .similar import similar_nodes
+                if h is None:
+                    h = model.propagate(test_set=test_set)
+                sim = similar_nodes(model, src, int(n_similar), table=similar_table, metric=similar_metric,
+                                    exclude=exclude, exclude_self=exclude_self, test_set=test_set, h=h)
+                if candidates == "similar":
+                    n_cand, fill = similar_candidates(src, sim)
+                else:
+                    both, make_fill = union_candidates(n, src, ppr, min_ppr, _exclusion(model, exclude, adj, dev),
+                                                       exclude_self, sim, split_threshold)
+                    n_cand = both[0]
+            elif candidates == "2hop":
                 if exclude not in ("adj", None):
                     raise ValueError("candidates='2hop' takes exclude='adj' or None: the two-hop row kernel drops the "
                                      "row of the adjacency it walks")
@@ -218,7 +307,11 @@ def recommend(model, score_func, sources, k: int = 100, *, candidates="ppr", min
             else:
                 n_cand, fill = generate_candidates(n, src, ppr if candidates == "ppr" else None, min_ppr,
                                                    _exclusion(model, exclude, adj, dev), exclude_self, split_threshold)
-            counts_host = n_cand.cpu().numpy()       # the one read-back: it sizes the chunks and their outputs
+            if candidates == "ppr+similar":          # (the PPR candidates' counts ride in the same read-back)
+                counts_host, ppr_host = both.cpu().numpy()
+                fill = make_fill(ppr_host)
+            else:
+                counts_host = n_cand.cpu().numpy()   # the one read-back: it sizes the chunks and their outputs
         if h is None:
             h = model.propagate(test_set=test_set)
         ids = torch.full((S, k), -1, dtype=torch.int64, device=dev)
