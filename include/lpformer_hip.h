@@ -1247,6 +1247,58 @@ int lpf_similar_topm_f32(int64_t S, int64_t n, int32_t D, const float *Q, int64_
                          void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-node structure (node_structure.hip): degree, core number, connected component and triangle count of every node --
+ * where a pair's endpoints sit in the graph, and the numbers of a dataset table.  The reference has no such code.  The
+ * five symbols were added within ABI 16: the addition changes no existing symbol, so LPF_ABI_VERSION stays.
+ *
+ * The graph is the simple undirected graph of a CSR with sorted, unique int32 columns and a SYMMETRIC pattern (values
+ * ignored; a non-symmetric pattern is outside the contract): u ~ v iff u != v and v is in row u.  Stored self-loops
+ * change nothing: every kernel skips col == row.  Every result is a pure function of the graph: not of the launch
+ * shape, of how many launches the caller queues between read-backs, or of timing; two runs are bitwise equal.
+ * Integers only; no workgroup waits on another; nothing is read back.  Common limits (LPF_ERR_INVALID otherwise,
+ * before any launch): 0 <= n < 2^31 - 1, 0 <= nnz < 2^31 - 1, no NULL array (col / row may be NULL when nnz == 0).
+ * n == 0 returns LPF_OK without a launch.  Row pointers outside [0, nnz] and columns outside [0, n) read as absent.
+ * ---------------------------------------------------------------------------------------------- */
+/* Rows longer than this are the caller's to list for lpf_core_sweep (one workgroup each); shorter ones share a
+ * wavefront, eight lanes per row. */
+#define LPF_CORE_LONG_ROW 64
+/* hv_form of lpf_core_sweep: how a LISTED row finds H_v.  DEFAULT: an LDS histogram of min(est[u], est[v]) and a suffix
+ * scan while est[v] < 4096, bisection above; BISECT: bisection on h with a workgroup count per pass, always (kept to
+ * be measured against: tools/node_structure_time.py).  Both give the same estimates. */
+#define LPF_CORE_FORM_DEFAULT 0
+#define LPF_CORE_FORM_BISECT 1
+/* degree int32[n]: the neighbours of each node other than itself. */
+int lpf_node_degree(int64_t n, int64_t nnz, const int64_t *rowptr, const int32_t *col, int32_t *degree, void *stream);
+/* ONE in-place sweep of the h-index iteration on est int32[n] (the caller starts it as the degree):
+ * est[v] <- min(est[v], H_v), H_v = the largest h such that at least h neighbours u have est[u] >= h.  A node whose
+ * estimate drops stores it and is counted in *changed (one int32, NOT zeroed here; one integer atomic per wavefront at
+ * most).  long_rows int32[n_long]: every row of more than LPF_CORE_LONG_ROW entries, each once (a row that is missing
+ * is never updated).  A sweep that leaves *changed untouched has found the fixpoint, which is the core number whatever
+ * mixture of old and new neighbour estimates the lanes of earlier sweeps read: estimates start as upper bounds and
+ * only fall, H of upper bounds is an upper bound, and at a sweep that stored nothing every est[v] <= H_v, so {est >= k}
+ * induces a subgraph of minimum degree >= k for each k. */
+int lpf_core_sweep(int64_t n, int64_t nnz, const int64_t *rowptr, const int32_t *col, const int32_t *long_rows,
+                   int64_t n_long, int32_t hv_form, int32_t *est, int32_t *changed, void *stream);
+/* Connected components on parent int32[n] (the caller starts it as the identity), a round = hook, then jump.
+ * hook: one lane per stored entry (row[e], col[e]) -- row int32[nnz] is the row id of every entry --: where
+ * parent[u] < parent[v], an agent-scope integer atomic min of parent[u] into parent[parent[v]] and into parent[v]; every
+ * word that fell is counted in *changed (as above).  jump: parent[v] <- the root of v's chain (parent[x] <= x always,
+ * so the chain falls strictly; at most n steps).  A hook that leaves *changed untouched ends the loop: every entry then
+ * joins equal labels and every label is a root, and since labels only fall, to labels of their own component, and the
+ * smallest node of a component can never be relabelled, parent[v] is the SMALLEST NODE ID of v's component. */
+int lpf_components_hook(int64_t n, int64_t nnz, const int32_t *row, const int32_t *col, int32_t *parent,
+                        int32_t *changed, void *stream);
+int lpf_components_jump(int64_t n, int32_t *parent, void *stream);
+/* triangles int64[n]: the triangles through each node.  For every stored entry with row < col, c = |N(u) & N(v)| without
+ * u and v (the sorted-row intersection of lpf_pair_heuristics_f32: the shorter row walked, the longer binary-searched)
+ * is added to both endpoints with 64-bit integer atomics, and a last launch halves the sums (each triangle through a
+ * node arrives over two of its edges): exact in any order.  An entry that walks more than split_threshold columns
+ * (negative: LPF_HEUR_SPLIT_DEFAULT) is listed and gets a 256-thread workgroup of its own, so a hub row does not
+ * serialise a wavefront.  scratch: int32[1 + nnz] (the list), written by this call only; triangles is zeroed here. */
+int lpf_node_triangles(int64_t n, int64_t nnz, const int64_t *rowptr, const int32_t *row, const int32_t *col,
+                       int32_t split_threshold, int32_t *scratch, int64_t *triangles, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host side (liblpformer_host.so)
  * ---------------------------------------------------------------------------------------------- */
 

@@ -16,8 +16,13 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
                                         (device spread-and-expand kernel): what there was to select, per node class;
                                         elph_features (the ELPH / BUDDY layout), ball_jaccard, hop_counts_reference
                                         (numpy restatement)
+    node_structure                      degree, core number, component (smallest id) and triangle count of every node
+                                        (device h-index sweeps, hook-and-jump, sorted-row intersection): NodeStructure
+                                        (clustering, component_size, summary), pair_node_values / same_component (the
+                                        per-pair axis for metrics_by_bin), DEGREE_BINS, CORE_BINS, structure_reference
+                                        (numpy / scipy restatement)
     recommend                           top-K new links per source node (device candidates, scoring, top-K)
-    similar_nodes                       the m nodes nearest to each query by inner product or cosine over the encoder's
+    similar_nodes                      the m nodes nearest to each query by inner product or cosine over the encoder's
                                         output, the raw features or any table (device matrix-core kernel with the top-m
                                         kept in LDS: no [S, n] matrix); Similar, similar_reference (numpy restatement)
     explain, explain_from_scores        per-pair attention attribution: top nodes, mass per type, entropy (device
@@ -58,6 +63,8 @@ from .ppr import calc_ppr, calc_ppr_gpu, get_ppr, load_or_calc_ppr, ppr_coo  # n
 from .pyg_api import LPFormer  # noqa: F401
 from .recommend import Recommendations, recommend  # noqa: F401
 from .similar import Similar, similar_nodes, similar_reference  # noqa: F401
+from .structure import (CORE_BINS, DEGREE_BINS, NodeStructure, node_structure, pair_node_values,  # noqa: F401
+                        same_component, structure_reference)
 from .threshold_profile import ThresholdProfile, suggest_thresholds, threshold_profile  # noqa: F401
 
 __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_ppr_gpu", "get_ppr",
@@ -69,4 +76,5 @@ __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_
            "pair_katz", "katz_from_walks", "walks_reference", "negative_rows", "negative_pairs", "UniformNegatives",
            "negatives_reference", "link_split", "pair_hop_counts", "hop_counts_reference", "elph_features",
            "ball_jaccard", "bootstrap_sums", "bootstrap_sums_reference", "bootstrap_metrics", "compare_metrics",
-           "bootstrap_by_bin", "similar_nodes", "similar_reference", "Similar"]
+           "bootstrap_by_bin", "similar_nodes", "similar_reference", "Similar", "node_structure", "NodeStructure",
+           "structure_reference", "pair_node_values", "same_component", "DEGREE_BINS", "CORE_BINS"]

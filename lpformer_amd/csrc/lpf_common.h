@@ -144,6 +144,28 @@ __device__ __forceinline__ bool lpf_sorted_has(const int32_t *__restrict__ col, 
     return i < hi && col[i] == key;
 }
 
+// The sorted-row intersection of a pair (pair_heuristics.hip, node_structure.hip): the pair walks its SHORTER row (on
+// equal lengths the row of min(a, b)) and binary-searches each walked column in the other row.
+struct LpfPairRows {
+    int64_t r0, q0;   // first entry of the walked row / the probed row
+    int32_t len, qlen;
+};
+
+// The walked and the probed row of (a, b); both empty when an id lies outside [0, n).
+__device__ __forceinline__ LpfPairRows lpf_pair_rows(int64_t a, int64_t b, int64_t n,
+                                                     const int64_t *__restrict__ rowptr) {
+    LpfPairRows r{0, 0, 0, 0};
+    if ((uint64_t)a >= (uint64_t)n || (uint64_t)b >= (uint64_t)n) return r;
+    const int64_t a0 = rowptr[a], a1 = rowptr[a + 1], b0 = rowptr[b], b1 = rowptr[b + 1];
+    const int64_t da = a1 - a0, db = b1 - b0;
+    const bool walk_a = da < db || (da == db && a <= b);
+    r.r0 = walk_a ? a0 : b0;
+    r.len = (int32_t)(walk_a ? da : db);
+    r.q0 = walk_a ? b0 : a0;
+    r.qlen = (int32_t)(walk_a ? db : da);
+    return r;
+}
+
 // The flagged lanes of a wave append `item` to list[1 ..]; list[0] counts the entries: one ticket per wave, its lanes
 // take consecutive slots.  Call it wave-uniformly.
 __device__ __forceinline__ void lpf_wave_list_push(int32_t *__restrict__ list, bool flag, int32_t item) {

@@ -26,25 +26,6 @@ constexpr int HEUR_BLOCK = 256;                 // 4 wavefronts
 constexpr int HEUR_WAVES = HEUR_BLOCK / LPF_WAVE;
 constexpr int HEUR_LONG_GRID = 2048;            // persistent workgroups of the long-pair kernel
 
-struct PairRows {
-    int64_t r0, q0;   // first entry of the walked row / the probed row
-    int32_t len, qlen;
-};
-
-// The walked and the probed row of (a, b); both empty when an id lies outside [0, n).
-__device__ __forceinline__ PairRows pair_rows(int64_t a, int64_t b, int64_t n, const int64_t *__restrict__ rowptr) {
-    PairRows r{0, 0, 0, 0};
-    if ((uint64_t)a >= (uint64_t)n || (uint64_t)b >= (uint64_t)n) return r;
-    const int64_t a0 = rowptr[a], a1 = rowptr[a + 1], b0 = rowptr[b], b1 = rowptr[b + 1];
-    const int64_t da = a1 - a0, db = b1 - b0;
-    const bool walk_a = da < db || (da == db && a <= b);
-    r.r0 = walk_a ? a0 : b0;
-    r.len = (int32_t)(walk_a ? da : db);
-    r.q0 = walk_a ? b0 : a0;
-    r.qlen = (int32_t)(walk_a ? db : da);
-    return r;
-}
-
 __device__ __forceinline__ void write_out(int64_t p, int32_t c, double sa, double sr, int32_t *__restrict__ cn,
                                           float *__restrict__ aa, float *__restrict__ ra) {
     if (cn) cn[p] = c;
@@ -61,8 +42,8 @@ __global__ __launch_bounds__(HEUR_BLOCK) void heur_short_kernel(
     if (wave0 >= P) return;                        // wave-uniform
     const int64_t p = wave0 + lane;
     const bool live = p < P;
-    PairRows r{0, 0, 0, 0};
-    if (live) r = pair_rows(pairs[p], pairs[ld + p], n, rowptr);
+    LpfPairRows r{0, 0, 0, 0};
+    if (live) r = lpf_pair_rows(pairs[p], pairs[ld + p], n, rowptr);
     const bool is_long = live && r.len > thr;
 
     lpf_wave_list_push(long_list, is_long, (int32_t)p);
@@ -136,7 +117,7 @@ __global__ __launch_bounds__(HEUR_BLOCK) void heur_long_kernel(
     const int32_t n_long = long_list[0];
     for (int32_t li = blockIdx.x; li < n_long; li += gridDim.x) {   // block-uniform
         const int64_t p = long_list[1 + li];
-        const PairRows r = pair_rows(pairs[p], pairs[ld + p], n, rowptr);
+        const LpfPairRows r = lpf_pair_rows(pairs[p], pairs[ld + p], n, rowptr);
         const int64_t qend = r.q0 + r.qlen;
         int64_t lo = r.q0;                        // this thread's keys grow: its lower bounds never move back
         int32_t c = 0;
