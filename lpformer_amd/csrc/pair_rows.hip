@@ -94,6 +94,27 @@ struct RowsArgs {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
+// Inclusive scan of an int over the wavefront (all 64 lanes active), for the set-up: shifts inside a row of 16 lanes, then
+// lane 15 of a row broadcast into the next row and lane 31 into the upper half.  Six DPP additions: no LDS round trip
+// per step (__shfl_up compiles to ds_bpermute_b32: the first chunk's ten scans were sixty DEPENDENT permutes, 2.5 us on
+// the one wavefront every other waits for -- profiles/rows_setup_stamps.txt), and no permute addresses that could be
+// hoisted and kept alive across the unit walk (EXPERIMENTS round 6, point ii).
+__device__ __forceinline__ int pr_wave_scan(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);    // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);    // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);    // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);    // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
+    return v;
+}
+// A copy of a thread id the compiler cannot see through: what is derived from it is computed where it is used, not hoisted
+// out of the loop around it.
+__device__ __forceinline__ int pr_opaque(int v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
 // (tuning builds, -DPR_STAMPS: wall-clock marks -- 100 MHz -- of lane 0 of every wavefront; tools/rows_stamps.py)
 #ifdef PR_STAMPS
 __device__ uint64_t *pr_stamp_buf = nullptr;
@@ -313,6 +334,12 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
             if (i < 3 * GG) lvec[i] = tv[u];
         }
         if (ft < 24) lstat[ft] = ts;
+        if constexpr (PT) {
+            // the first chunk's units start right behind the barrier below: every flag and the counters are cleared here,
+            // before the number of units is known
+            for (int k = tid; k < PR_FLAGS; k += NTH) lflag[k] = 0;
+            if (tid < 4) lctl[tid] = 0;
+        }
     }
 
     // pair-major position of pair p's first entry (the pointers clamped into their regions)
@@ -352,15 +379,21 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
             const int64_t target = (total * b) / (int64_t)gridDim.x;
             int64_t P = 0, C = 0;
             int NE = 0;
-            if (b >= (int64_t)gridDim.x) {
-                P = A.bs; C = (total - A.bs) / EW; NE = total_ne;
-            } else if (b > 0 && target > 0) {   // (target 0: fewer entries + pairs than workgroups, nothing in front)
+            // more entries than the scratch for the pieces has units for: nothing is walked, the rows are NaN and
+            // the sticky bit tells the caller to size the workspace again (as when the selection does not fit)
+            const bool over_w = (total - A.bs) / EW > 16 * (A.units_cap - 1);
+            // the block B the end lies in, the weight f and the pairs with entries nef in front of it (nothing in front --
+            // workgroup 0, or target 0: fewer entries + pairs than workgroups -- block 0 and no cut inside it)
+            const bool past = b >= (int64_t)gridDim.x, cut = !past && b > 0 && target > 0;
+            int64_t B = 0, f = 0;
+            int nef = 0;
+            if (cut) {
                 // last block B with (weight in front of B) < target: it lies in the share with ex < target <= ex + own
                 const int64_t ex = x - own_w;
                 const uint64_t holder = __ballot(ex < target && target <= x);
                 const int hl = holder ? __builtin_ctzll(holder) : 0;
-                int64_t B = (int64_t)lane * per, f = ex;
-                int nef = xn - own_ne;
+                B = (int64_t)lane * per; f = ex;
+                nef = xn - own_ne;
                 if (lane == hl) {
                     // (the share's first blocks from registers -- no round trip per step; the rest, if any, from memory)
                     const int64_t lim = (int64_t)(lane + 1) * per < nblk ? (int64_t)(lane + 1) * per : nblk;
@@ -385,32 +418,88 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
                 B = __shfl(B, hl, 64);
                 f = __shfl(f, hl, 64);
                 nef = __shfl(nef, hl, 64);
-                const int64_t p = B * SB + lane;
-                const int cnt = p < A.bs ? pt_count(p) : 0;
-                int xs = cnt;     // inclusive scan of the entries
+            }
+            if (past) {
+                P = A.bs; C = (total - A.bs) / EW; NE = total_ne;
+            } else if (wave == 1) {
+                if (cut) {
+                    const int64_t p = B * SB + lane;
+                    const int cnt = p < A.bs ? pt_count(p) : 0;
+                    int xs = cnt;     // inclusive scan of the entries
 #pragma unroll
-                for (int dlt = 1; dlt < 64; dlt <<= 1) {
-                    const int y = __shfl_up(xs, dlt, 64);
-                    if (lane >= dlt) xs += y;
+                    for (int dlt = 1; dlt < 64; dlt <<= 1) {
+                        const int y = __shfl_up(xs, dlt, 64);
+                        if (lane >= dlt) xs += y;
+                    }
+                    // f(p) = f + lane + EW * (entries of the block's pairs in front of p)
+                    const bool below = p < A.bs && f + lane + (int64_t)EW * (xs - cnt) < target;
+                    const uint64_t bm = __ballot(below);      // (monotone: the first c pairs are below the target)
+                    const int c = __popcll(bm);
+                    const int before = c == 0 ? 0 : __shfl(xs, c - 1, 64);
+                    P = B * SB + c;
+                    // entries in front of P: in front of block B (f = EW * entries + pairs = EW * entries + B * SB) + inside it
+                    C = (f - B * SB) / EW + before;
+                    NE = nef + __popcll(__ballot(below && cnt > 0));
                 }
+            } else {
+                // Lower end: the range starts inside block B, so B's 64 table entries and the PR_CHUNK pairs behind them
+                // ARE the first chunk -- requested in one go (row i of lane l: pair 64 B + l + 64 i, clamped into the
+                // table), cut like the upper end, and staged by this wavefront alone: no second round trip behind a
+                // barrier, no scan through the workgroup.
+                static_assert(PR_CHUNK % SB == 0 && SB == 64, "a row of the first chunk is a block of pairs");
+                constexpr int NR = PR_CHUNK / SB + 1;
+                const int64_t pb = B * SB + lane;
+                int4 e[NR];
+#pragma unroll
+                for (int i = 0; i < NR; ++i) {
+                    const int64_t p = pb + SB * i;
+                    e[i] = A.pair_tab[p < A.bs ? p : A.bs - 1];
+                }
+                int cr[NR];      // entries of the row's pair (as pt_count: an entry outside the buffer counts as empty)
+#pragma unroll
+                for (int i = 0; i < NR; ++i) {
+                    const int64_t ce = (int64_t)e[i].y + e[i].z + e[i].w;
+                    const bool okr = pb + SB * i < A.bs &&
+                                     !(e[i].x < 0 || e[i].y < 0 || e[i].z < 0 || e[i].w < 0 || e[i].x + ce > A.ent_cap);
+                    cr[i] = okr ? (int)ce : 0;
+                }
+                const int cnt = cr[0];
+                const int xs = pr_wave_scan(cnt);
                 // f(p) = f + lane + EW * (entries of the block's pairs in front of p)
-                const bool below = p < A.bs && f + lane + (int64_t)EW * (xs - cnt) < target;
-                const uint64_t bm = __ballot(below);      // (monotone: the first c pairs are below the target)
-                const int c = __popcll(bm);
+                const bool below = cut && pb < A.bs && f + lane + (int64_t)EW * (xs - cnt) < target;
+                const int c = __popcll(__ballot(below));  // (monotone: the first c pairs are below the target)
                 const int before = c == 0 ? 0 : __shfl(xs, c - 1, 64);
                 P = B * SB + c;
-                // entries in front of P: in front of block B (f = EW * entries + pairs = EW * entries + B * SB) + inside it
                 C = (f - B * SB) / EW + before;
                 NE = nef + __popcll(__ballot(below && cnt > 0));
+                // pair k = 64 i + lane - c of the chunk: ltp[k] = first entry, ltp[TPS + k] / ltp[2 TPS + k] = common
+                // neighbours / one-hop nodes, lcum[k] = the entries in front of it inside the chunk (a scan per row, the
+                // row's total carried into the next).  All PR_CHUNK candidates: where the range ends is the other
+                // wavefront's to find, cn and lcum[cn] are read behind the barrier.
+                int run = 0;
+#pragma unroll
+                for (int i = 0; i < NR; ++i) {
+                    const int k = SB * i + lane - c;
+                    const bool in = k >= 0 && k < PR_CHUNK;
+                    const int ck = (in && !over_w) ? cr[i] : 0;
+                    const bool ok = ck > 0;
+                    const int sk = pr_wave_scan(ck);
+                    if (in) {
+                        ltp[k] = ok ? e[i].x : 0;
+                        ltp[TPS + k] = ok ? e[i].y : 0;
+                        ltp[2 * TPS + k] = ok ? e[i].z : 0;
+                        lcum[k] = run + sk - ck;
+                    }
+                    run += __builtin_amdgcn_readlane(sk, 63);
+                }
+                if (lane == 0) lcum[PR_CHUNK] = run;
             }
             if (lane == 0) {
                 lctl[4 + 2 * wave] = (int)(P & 0xffffffff); lctl[5 + 2 * wave] = (int)(P >> 32);
                 lctl[12 + 2 * wave] = (int)(C & 0xffffffff); lctl[13 + 2 * wave] = (int)(C >> 32);
                 if (wave == 0) {
                     lctl[8] = NE; lctl[9] = 0; lctl[10] = total_ne;   // pairs with entries in front of the range, in all
-                    // more entries than the scratch for the pieces has units for: nothing is walked, the rows are NaN and
-                    // the sticky bit tells the caller to size the workspace again (as when the selection does not fit)
-                    const bool over = (total - A.bs) / EW > 16 * (A.units_cap - 1);
+                    const bool over = over_w;
                     lctl[11] = over ? 1 : 0;
                     if (over && blockIdx.x == 0 && A.sel_ctl)
                         atomicOr(reinterpret_cast<unsigned long long *>(const_cast<int64_t *>(A.sel_ctl) + 3),
@@ -574,26 +663,36 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
 
     for (int64_t c0 = P0; c0 < P1; c0 += PR_CHUNK) {
         const int cn = (int)(P1 - c0 < PR_CHUNK ? P1 - c0 : PR_CHUNK);
-        // PT: the chunk's table entries are requested in front of the barrier (they travel while the last wavefront
-        // arrives; the barrier guards LDS, not them)
-        constexpr int PER = (PR_CHUNK + NTH - 1) / NTH;
-        int4 e_pre[PER];
-        if constexpr (PT) {
+        // PT: a range's FIRST chunk was staged by wavefront 0 in front of the barrier above (all PR_CHUNK candidates, the
+        // flags and counters cleared beside the table fill): what is left is to cut it at the range's end
+        const bool staged = PT && c0 == P0;
+        int64_t v0, v1;
+        if (staged) {
+            v0 = vpos;
+            v1 = vpos + lcum[cn];
+            vpos = v1;
+        } else if constexpr (PT) {
+            // the chunk's table entries are requested in front of the barrier (they travel while the last wavefront
+            // arrives; the barrier guards LDS, not them)
+            constexpr int PER = (PR_CHUNK + NTH - 1) / NTH;
+            // (thread and wavefront ids through opaque copies: what this staging derives from them -- the sixteen
+            //  comparisons of the scan below, LDS addresses -- is computed here, where a second chunk needs it, and not
+            //  hoisted in front of the chunk loop, where every first chunk paid for it and it lived -- fifty spilled
+            //  scalar registers -- across the units)
+            const int tid_o = pr_opaque(tid), wave_o = pr_opaque(wave);
+            int4 e_pre[PER];
 #pragma unroll
             for (int i = 0; i < PER; ++i) {
-                const int k = tid * PER + i;
+                const int k = tid_o * PER + i;
                 e_pre[i] = A.pair_tab[c0 + (k < cn ? k : cn - 1)];
             }
-        }
-        lpf_lds_barrier();   // the previous chunk's lists and pointers are no longer needed
-        int64_t v0, v1;
-        if constexpr (PT) {
+            lpf_lds_barrier();   // the previous chunk's lists and pointers are no longer needed
             // ltp[k] = first entry, ltp[TPS + k] / ltp[2 TPS + k] = common neighbours / one-hop nodes of pair k, lcum = the
             // entries in front of pair k inside the chunk (a scan over the workgroup)
             int cnt[PER], own = 0;
 #pragma unroll
             for (int i = 0; i < PER; ++i) {
-                const int k = tid * PER + i;
+                const int k = tid_o * PER + i;
                 cnt[i] = 0;
                 if (k < cn) {
                     const int4 e = e_pre[i];
@@ -606,32 +705,28 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
                 }
                 own += cnt[i];
             }
-            int x = own;
-#pragma unroll
-            for (int dlt = 1; dlt < 64; dlt <<= 1) {
-                const int y = __shfl_up(x, dlt, 64);
-                if (lane >= dlt) x += y;
-            }
-            if (lane == 63) lwcnt[wave] = x;
-            if (tid < 4) lctl[tid] = 0;
+            const int x = pr_wave_scan(own);
+            if (lane == 63) lwcnt[wave_o] = x;
+            if (tid_o < 4) lctl[tid_o] = 0;
             lpf_lds_barrier();
             int pre = 0, tot = 0;
             for (int w = 0; w < NTH / 64; ++w) {
-                if (w < wave) pre += lwcnt[w];
+                if (w < wave_o) pre += lwcnt[w];
                 tot += lwcnt[w];
             }
             int run = pre + x - own;
 #pragma unroll
             for (int i = 0; i < PER; ++i) {
-                const int k = tid * PER + i;
+                const int k = tid_o * PER + i;
                 if (k < cn) lcum[k] = run;
                 run += cnt[i];
             }
-            if (tid == 0) lcum[cn] = tot;
+            if (tid_o == 0) lcum[cn] = tot;
             v0 = vpos;
             v1 = vpos + tot;
             vpos = v1;
         } else {
+        lpf_lds_barrier();   // the previous chunk's lists and pointers are no longer needed
         for (int i = tid; i < 3 * (cn + 1); i += NTH) {
             const int t = i / (cn + 1), k = i % (cn + 1);
             int64_t v = A.type_ptr[(int64_t)t * (A.bs + 1) + c0 + k];
@@ -652,9 +747,12 @@ __global__ __launch_bounds__(NTH, NTH >= 512 ? 4 : 3) void pair_rows_kernel(cons
         // units in front of it are flagged done (they were drawn earlier: nobody waits for a later unit) -- no barrier,
         // no separate merge phase.  Only a chunk of more than PR_FLAGS units falls back to barrier + merge list.
         const bool inl = n_units <= PR_FLAGS;
-        if (inl)
-            for (int k = tid; k < n_units; k += NTH) lflag[k] = 0;
-        lpf_lds_barrier();
+        if (!staged) {
+            const int tid_f = pr_opaque(tid);   // (as in the staging above: nothing of this hoisted in front of the chunk loop)
+            if (inl)
+                for (int k = tid_f; k < n_units; k += NTH) lflag[k] = 0;
+            lpf_lds_barrier();
+        }
         PR_STAMP(2);
         PR_STAMP(3);
         // ---- the chunk's units: 16 consecutive entries of the pair-major order each, EPW of them per wavefront and
