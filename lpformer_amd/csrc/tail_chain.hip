@@ -5,9 +5,9 @@
 //   C  s   = w_s1 . ReLU( A_e r_e + A_p r_p + c ) + b_s1 ; sigmoid       score head with the boundary Linears folded
 //
 // Same machinery as dense_chain.hip (samples on the MFMA columns, a pair of wavefronts per 16 samples splitting the
-// feature tiles, weights host-packed in A-operand order and staged global -> registers -> LDS one k-group ahead,
-// double-buffered, one barrier per stage), with three stages chained through LDS: a stage's accumulators, written in
-// accumulator layout, are the next stage's B operands.  What the stage boundaries read besides -- biases, LayerNorm
+// feature tiles, weights host-packed in A-operand order and staged global -> registers -> LDS ahead of the MFMAs,
+// double-buffered, one barrier per stage -- here as one stream through all stages, see TC_PIN), with three stages
+// chained through LDS: a stage's accumulators, written in accumulator layout, are the next stage's B operands.  What the stage boundaries read besides -- biases, LayerNorm
 // weights, w_dot -- is requested once at the start of the workgroup and waits in LDS.  Stage B appends one k-group read from global memory (the
 // count features), stage C starts with k-groups read from global memory (r_e, produced on the side stream by the
 // elementwise branch).  Against three separate launches this removes two launch ramps and the round trips of the
@@ -22,6 +22,7 @@
 // E -> C over r_e -> (64 pairs without selected nodes: epilogue, done) -> A -> B -> C over r_p -> epilogue.  Stage C
 // sums in the order it always did (r_e k-groups first), so the scores are bitwise those of the separate launches.
 #include <type_traits>
+#include <utility>
 
 #include "lpf_common.h"
 
@@ -84,8 +85,10 @@ constexpr int tc_stage_stride(int ntp) { return (ntp * 64 + 511) / 512 * 512; }
 // weight elements: one per (tile, lane) and k-group -- four fp32 (f32x4) or, in the bf16 variant, four bf16 (uint2) of
 // W[16 c + i][16 ks + 4 q .. + 3]
 typedef short bf16x4_bits __attribute__((ext_vector_type(4)));
-template <int P, int NTP, typename T>
-__device__ __forceinline__ void tc_load(T (&r)[P], const float *packed, int stage, int tid) {
+// (one register stage serves every weight stream of the kernel: PM elements, a stream uses the first P)
+template <int P, int NTP, int PM, typename T>
+__device__ __forceinline__ void tc_load(T (&r)[PM], const float *packed, int stage, int tid) {
+    static_assert(P <= PM, "the register stage holds a weight stage");
     const T *src = reinterpret_cast<const T *>(packed) + (int64_t)stage * tc_stage_stride(NTP);
 #pragma unroll
     for (int e = 0; e < P; ++e) {
@@ -98,49 +101,101 @@ __device__ __forceinline__ void tc_load(T (&r)[P], const float *packed, int stag
 #endif
     }
 }
-template <int P, typename T>
-__device__ __forceinline__ void tc_store(const T (&r)[P], T *slab, int tid) {
+template <int P, int PM, typename T>
+__device__ __forceinline__ void tc_store(const T (&r)[PM], T *slab, int tid) {
+    static_assert(P <= PM, "the register stage holds a weight stage");
 #pragma unroll
     for (int e = 0; e < P; ++e) slab[e * TC_THREADS + tid] = r[e];
 }
 
-// The k-loops mean "barrier, request k-group kg + 1, MFMAs of kg".  In the unrolled loops of stage E and of stage C over
-// r_p the scheduler, left alone, sinks the request to the end of the k-group -- directly in front of its own wait, the
-// store and the next barrier, one exposed L2 round trip per k-group -- and pulls the next store and barrier into the
-// MFMA stream.  Nothing is scheduled across a TC_PIN(): one behind the request keeps it in front of the MFMAs, one at
-// the end of the k-group keeps the wait behind them.  The rolled loops and stage B keep the order by themselves
-// (tools/tail_isa.py counts the MFMAs between every request and its wait, per instantiation); pinned as well they
-// measured slower (EXPERIMENTS.md), so they are left to the scheduler.
+// The weights are ONE stream through the kernel, two stages ahead of the MFMAs: while k-group kg runs out of one slab,
+// stage kg + 1 -- requested a k-group earlier -- goes from the registers to the other slab, and stage kg + 2 is
+// requested into the same registers.  A k-group is
+//     operand reads | its first MFMAs | wait for kg + 1, store it, request kg + 2 | the other MFMAs | barrier
+// so nothing but the wait for the store's completion stands between a k-group's last MFMA and the barrier, and nothing
+// but the operand reads between the barrier and the next k-group's first MFMA: the store, its wait for the weights and
+// the request's address arithmetic run under the matrix pipe.  The other slab is free by then -- every wavefront read
+// its operands of kg - 1 before the MFMAs it issued in front of the barrier that ended kg - 1.  The stream runs across
+// the stage boundaries: a stage's last two k-groups store and request the next stage's first two weight stages, so a
+// stage starts with its weights published and no round trip of its own.  A stage's last k-group has no barrier where
+// the boundary behind it (a LayerNorm exchange, the publication of the hidden tiles) brings one anyway.
+// Nothing is scheduled across a TC_PIN(); the scheduler, left alone, sinks the request to the end of the k-group and
+// pulls the store and the barrier into the MFMA stream (tools/tail_isa.py reads the order back from the assembly).
 #define TC_PIN() __builtin_amdgcn_sched_barrier(0)
+struct TcNoStep { __device__ __forceinline__ void operator()() const {} };
+// the barrier between two k-groups of a stage (tools/tail_isa.py knows the k-groups by it)
+__device__ __forceinline__ void tc_kgroup_barrier() { __syncthreads(); }
+// f(kg) for kg = 0, STEP, .. < N with kg a constant expression: which stream a k-group's weight step serves is decided
+// per k-group at compile time (as run-time branches of an unrolled loop the two requests are merged into one with a
+// selected address, and the assembly no longer says which call made a load)
+template <int STEP, typename F, int... I>
+__device__ __forceinline__ void tc_each_impl(F &f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I * STEP>()), ...);
+}
+template <int N, int STEP = 1, typename F>
+__device__ __forceinline__ void tc_each(F f) {
+    tc_each_impl<STEP>(f, std::make_integer_sequence<int, (N + STEP - 1) / STEP>());
+}
 
 // acc[c] += W[16 (c0 + c) + i][k-group] * bv for this wave's TPW tiles; lw = slab + c0 * 64 + lane.  last = false (the
 // same for the whole wavefront): the wave's last tile is padding -- all-zero weight rows -- and is left out.
-template <int TPW>
-__device__ __forceinline__ void tc_mfma(f32x4 (&acc)[TPW], const f32x4 *lw, const f32x4 bv, bool last = true) {
-    f32x4 a[TPW];
+// step(): the weight stream's store and request of this k-group, run behind the k-group's first MFMAs.
+template <int TPW, typename Step = TcNoStep>
+__device__ __forceinline__ void tc_mfma(f32x4 (&acc)[TPW], const f32x4 *lw, const f32x4 bv, bool last = true,
+                                        Step step = Step()) {
+    // (eight tiles and more go four at a time: with all their operands read at once the D = 128 forms no longer fit
+    //  128 registers beside the weight stage that now stays in flight through the whole k-group; an accumulator still
+    //  takes its four MFMAs in ascending k)
+    constexpr int H = TPW >= 8 ? 4 : TPW;
 #pragma unroll
-    for (int c = 0; c < TPW; ++c) a[c] = lw[c * 64];
+    for (int h = 0; h < TPW; h += H) {
+        f32x4 a[H];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {  // consecutive MFMAs go to different accumulators
+        for (int c = 0; c < H; ++c) a[c] = lw[(h + c < TPW ? h + c : TPW - 1) * 64];
 #pragma unroll
-        for (int c = 0; c < TPW - 1; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][u], bv[u], acc[c], 0, 0, 0);
-        if (last) acc[TPW - 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[TPW - 1][u], bv[u], acc[TPW - 1], 0, 0, 0);
+        for (int u = 0; u < 4; ++u) {  // consecutive MFMAs go to different accumulators
+            // (the tile that may be padding goes first: what a wavefront that leaves it out has to restore then stands
+            //  in front of the other MFMAs, not between the k-group's last one and the barrier)
+            if (h + H >= TPW && last)
+                acc[TPW - 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[TPW - 1 - h][u], bv[u], acc[TPW - 1], 0, 0, 0);
+#pragma unroll
+            for (int c = 0; c < H; ++c)
+                if (h + c < TPW - 1) acc[h + c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][u], bv[u], acc[h + c], 0, 0, 0);
+            if constexpr (!std::is_same<Step, TcNoStep>::value) {
+                if (u == 0 && h == 0) {
+                    TC_PIN();
+                    step();
+                    TC_PIN();
+                }
+            }
+        }
     }
 }
 // bf16 variant: the four fp32 MFMAs of a k-group become ONE v_mfma_f32_16x16x16_bf16 -- a lane's four A values and
 // four B values (k = 4 q .. 4 q + 3 of the group) are exactly that instruction's operands; the activations are rounded
 // to bf16 here, the accumulation stays fp32.
-template <int TPW>
-__device__ __forceinline__ void tc_mfma(f32x4 (&acc)[TPW], const uint2 *lw, const f32x4 bv, bool last = true) {
+template <int TPW, typename Step = TcNoStep>
+__device__ __forceinline__ void tc_mfma(f32x4 (&acc)[TPW], const uint2 *lw, const f32x4 bv, bool last = true,
+                                        Step step = Step()) {
     bf16x4_bits b;
 #pragma unroll
     for (int u = 0; u < 4; ++u) b[u] = (short)lpf_f32_to_bf16(bv[u]);
+    uint2 w[TPW];
+#pragma unroll
+    for (int c = 0; c < TPW; ++c) w[c] = lw[c * 64];
 #pragma unroll
     for (int c = 0; c < TPW; ++c) {
         if (c == TPW - 1 && !last) break;
-        const uint2 w = lw[c * 64];
-        const bf16x4_bits a = {(short)(w.x & 0xffffu), (short)(w.x >> 16), (short)(w.y & 0xffffu), (short)(w.y >> 16)};
+        const bf16x4_bits a = {(short)(w[c].x & 0xffffu), (short)(w[c].x >> 16), (short)(w[c].y & 0xffffu),
+                               (short)(w[c].y >> 16)};
         acc[c] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, acc[c], 0, 0, 0);
+        if constexpr (!std::is_same<Step, TcNoStep>::value) {
+            if (c == 0) {
+                TC_PIN();
+                step();
+                TC_PIN();
+            }
+        }
     }
 }
 
@@ -241,7 +296,9 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     const float *peer_x = xch + (wave ^ 1) * 16 + j;
     float *vec = xch + S::XCH;
     f32x4 *my_hid = hid + (grp * S::HT) * 64 + lane;
-    int buf = 0;
+    int buf = 0;                // the slab the current k-group reads; the stream's next stage goes to the other one
+    WT wr[S::PM];               // the weight stream's register stage
+    WT *const slabs = reinterpret_cast<WT *>(lds);
 #ifdef TC_STAMPS
     uint64_t st_t[10] = {0};
     TC_STAMP(0);
@@ -311,7 +368,10 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     auto tc_rows_request = [&]() __attribute__((always_inline)) {
         if constexpr (ROWS) {
             const int fbase = 16 * half * TPWA + 4 * q;
-            const float *own = A.rows + mm * A.ldrows, *row = no_sel ? A.row_empty : own;
+            // (stage E form: a workgroup without selected nodes requests too -- every lane the first row, whose values
+            //  nobody takes -- so that the counted waits of the weight stream behind the request are the same on both
+            //  paths; with the request under a branch they become waits for everything)
+            const float *own = A.rows + (EW && lite ? 0 : mm * A.ldrows), *row = no_sel ? A.row_empty : own;
 #pragma unroll
             for (int c = 0; c < TPWA; ++c) {
                 const int f0 = fbase + 16 * c;
@@ -344,8 +404,8 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
         const int64_t gm = gpos < A.M ? gpos : A.M - 1;             // (a dead lane gathers what it would compute on)
         const int64_t gmm = A.perm ? A.perm[gm] : gm;
         int64_t ra = A.batch[gmm], rb = A.batch[A.batch_ld + gmm];
-        WT wrE[2];
-        tc_load<2, 2 * NTPA>(wrE, A.wE, 0, tid);
+        static_assert(S::PM >= 2 && S::PC <= S::PM && NGE >= 4, "stage E's weight stages fit the register stage");
+        tc_load<2, 2 * NTPA>(wr, A.wE, 0, tid);
         TC_PIN();   // (the first weights are requested next to the ids, not behind the eight pieces of the rows)
         if ((uint64_t)ra >= (uint64_t)A.n_rows) ra = 0;
         if ((uint64_t)rb >= (uint64_t)A.n_rows) rb = 0;
@@ -359,6 +419,11 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
             xra[i] = *reinterpret_cast<const f32x4 *>(xa + 32 * i);
             xrb[i] = *reinterpret_cast<const f32x4 *>(xb + 32 * i);
         }
+        // the stream's start: stage 0 waits for nothing but itself (the eight pieces stay in flight), stage 1 flies
+        // while the pieces arrive
+        tc_store<2>(wr, slabs + buf * S::SLAB, tid);
+        tc_load<2, 2 * NTPA>(wr, A.wE, 1, tid);
+        TC_PIN();
         tc_vec_publish();
         TC_STAMP_ROWS();
         {
@@ -367,27 +432,31 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
             for (int i = 0; i < NGE / 2; ++i) pe[2 * i * TE_KG] = xra[i] * xrb[i];
         }
         const f32x4 *my_pe = hid + (grp * S::HT) * 64 + (q >> 1) * TE_Q2 + (q & 1) * 16 + j;
+        __syncthreads();   // publishes the products, the boundary vectors and the first weight stage
         // (two k-groups per weight stage and barrier: a k-group of this layer is 512 float4, a slab holds 1,024; the
-        //  k-groups still reach an accumulator in ascending order.  The first barrier also publishes the products.)
-#pragma unroll
-        for (int kg = 0; kg < NGE; kg += 2) {
-            WT *lw = reinterpret_cast<WT *>(lds) + buf * S::SLAB;
-            tc_store<2>(wrE, lw, tid);
-            __syncthreads();
-            if (kg + 2 < NGE) tc_load<2, 2 * NTPA>(wrE, A.wE, kg / 2 + 1, tid);
-            TC_PIN();
+        //  k-groups still reach an accumulator in ascending order.  The last two weight steps are stage C's first two.)
+        tc_each<NGE, 2>([&](auto KG) __attribute__((always_inline)) {
+            constexpr int kg = decltype(KG)::value;
+            const WT *lw = slabs + buf * S::SLAB;
+            WT *nw = slabs + (buf ^ 1) * S::SLAB;
             const f32x4 bv0 = my_pe[kg * TE_KG], bv1 = my_pe[(kg + 1) * TE_KG];
-            tc_mfma<TPWA>(accE, lw + (half * TPWA) * 64 + lane, bv0);
+            tc_mfma<TPWA>(accE, lw + (half * TPWA) * 64 + lane, bv0, true, [&]() __attribute__((always_inline)) {
+                if constexpr (kg + 2 < NGE) tc_store<2>(wr, nw, tid);
+                else tc_store<S::PC>(wr, nw, tid);
+                if constexpr (kg + 4 < NGE) tc_load<2, 2 * NTPA>(wr, A.wE, kg / 2 + 2, tid);
+                else tc_load<S::PC, NTPC>(wr, A.wC, (kg + 4 - NGE) / 2, tid);
+            });
             tc_mfma<TPWA>(accE, lw + tc_stage_stride(NTPA) + (half * TPWA) * 64 + lane, bv1);
             TC_PIN();
             buf ^= 1;
-        }
+            if constexpr (kg + 2 < NGE) tc_kgroup_barrier();   // (behind the last k-group the LayerNorm's barriers follow)
+        });
         TC_STAMP(9);
         // stage A's rows: requested here, a LayerNorm and eight k-groups ahead of their use (the registers of the gathered
-        // rows are free from here on), instead of one more round trip in front of stage B
-        if (!lite) tc_rows_request();
-        WT wrCe[S::PC];
-        tc_load<S::PC, NTPC>(wrCe, A.wC, 0, tid);  // stage C's first weights fly during the epilogue
+        // rows are free from here on), instead of one more round trip in front of stage B.  Stage C's first weights are
+        // in their slab already, the second stage was requested in front of the rows: its wait leaves them in flight.
+        tc_rows_request();
+        TC_PIN();
         {   // bias -> LayerNorm -> ReLU: dense_chain.hip's epilogue 1, same operations in the same order
             const int fbase = 16 * half * TPWA + 4 * q;
 #pragma unroll
@@ -400,17 +469,33 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
         // ---- stage C over the r_e k-groups, r_e straight from LDS
 #pragma unroll
         for (int c = 0; c < TPWC; ++c) accC[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int kg = 0; kg < NGE; ++kg) {
-            WT *lw = reinterpret_cast<WT *>(lds) + buf * S::SLAB;
-            tc_store<S::PC>(wrCe, lw, tid);
-            __syncthreads();  // (kg == 0: also publishes stage E's hidden tiles)
-            if (kg + 1 < NGE) tc_load<S::PC, NTPC>(wrCe, A.wC, kg + 1, tid);
-            tc_mfma<TPWC>(accC, lw + (half * TPWC) * 64 + lane, my_hid[kg * 64]);
+        __syncthreads();   // publishes r_e (and the weight stage stored under stage E's last k-groups)
+        // (unrolled: the wait of k-group 0 leaves the rows in flight, which a loop's one wait for all trips cannot; the
+        //  last two weight steps of a workgroup that goes on are stage B's first two)
+        tc_each<NGE>([&](auto KG) __attribute__((always_inline)) {
+            constexpr int kg = decltype(KG)::value;
+            const WT *lw = slabs + buf * S::SLAB;
+            WT *nw = slabs + (buf ^ 1) * S::SLAB;
+            tc_mfma<TPWC>(accC, lw + (half * TPWC) * 64 + lane, my_hid[kg * 64], true, [&]() __attribute__((always_inline)) {
+                if constexpr (kg + 2 < NGE) {
+                    tc_store<S::PC>(wr, nw, tid);
+                    tc_load<S::PC, NTPC>(wr, A.wC, kg + 2, tid);
+                } else if (!lite) {
+                    if constexpr (kg + 1 < NGE) tc_store<S::PC>(wr, nw, tid);
+                    else tc_store<S::PB>(wr, nw, tid);
+                    if constexpr (kg + 2 == NGE) tc_load<S::PB, NTPB>(wr, A.wB, 0, tid);
+                    else tc_load<S::PB, NTPB>(wr, A.wB, 1, tid);
+                } else if constexpr (kg + 1 < NGE) {
+                    tc_store<S::PC>(wr, nw, tid);
+                }
+            });
+            TC_PIN();
             buf ^= 1;
-        }
+            // (behind the last k-group: every wave has read r_e, stage A may write the hidden tiles -- workgroup-uniform)
+            if constexpr (kg + 1 < NGE) tc_kgroup_barrier();
+            else if (!lite) __syncthreads();
+        });
         TC_STAMP(4);
-        if (!lite) __syncthreads();   // every wave has read r_e: stage A may write the hidden tiles  (workgroup-uniform)
     }
 
     if constexpr (ROWS) {
@@ -421,23 +506,45 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
             if constexpr (!EW) {
 #pragma unroll
             for (int c = 0; c < TPWC; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            WT wr[S::PC];
+            static_assert(NGE >= 2, "the stream's start requests two stages");
             const float *rer = A.re + mm * A.ldre + 4 * q;
             tc_load<S::PC, NTPC>(wr, A.wC, 0, tid);
-            f32x4 xr = *reinterpret_cast<const f32x4 *>(rer);
+            // r_e runs one k-group ahead: a group is requested in front of the weight stage of its step, so its wait at
+            // the head of the next k-group leaves that step's weights in flight.  Two registers take turns (k-groups
+            // in pairs): a loop that carries one copies it, and the copy waits for everything in front of the barrier.
+            f32x4 x0 = *reinterpret_cast<const f32x4 *>(rer), x1 = (f32x4){0.f, 0.f, 0.f, 0.f};
             tc_vec_publish();
-#pragma unroll 1
-            for (int kg = 0; kg < NGE; ++kg) {
-                const f32x4 bv = xr;
-                WT *lw = reinterpret_cast<WT *>(lds) + buf * S::SLAB;
-                tc_store<S::PC>(wr, lw, tid);
-                __syncthreads();
-                if (kg + 1 < NGE) {
-                    tc_load<S::PC, NTPC>(wr, A.wC, kg + 1, tid);
-                    xr = *reinterpret_cast<const f32x4 *>(rer + 16 * (kg + 1));
-                }
-                tc_mfma<TPWC>(acc, lw + (half * TPWC) * 64 + lane, bv);
+            tc_store<S::PC>(wr, slabs + buf * S::SLAB, tid);
+            tc_load<S::PC, NTPC>(wr, A.wC, 1, tid);
+            TC_PIN();
+            __syncthreads();
+            // (the last two steps store and request the last stage again: a step without a branch keeps the counted
+            //  waits, and nobody reads what it leaves)
+            auto group = [&](int kg, const f32x4 &xc, f32x4 &xn) __attribute__((always_inline)) {
+                const WT *lw = slabs + buf * S::SLAB;
+                WT *nw = slabs + (buf ^ 1) * S::SLAB;
+                tc_mfma<TPWC>(acc, lw + (half * TPWC) * 64 + lane, xc, true, [&]() __attribute__((always_inline)) {
+                    tc_store<S::PC>(wr, nw, tid);
+                    xn = *reinterpret_cast<const f32x4 *>(rer + 16 * (kg + 1 < NGE ? kg + 1 : NGE - 1));
+                    tc_load<S::PC, NTPC>(wr, A.wC, kg + 2 < NGE ? kg + 2 : NGE - 1, tid);
+                });
+                TC_PIN();
                 buf ^= 1;
+                if (kg + 1 < NGE) tc_kgroup_barrier();
+            };
+            static_assert(NGE % 2 == 0, "k-groups in pairs");
+            if constexpr (NGE == 8) {   // (D = 128: unrolled, every wait is counted for its own k-group)
+#pragma unroll
+                for (int kg = 0; kg < NGE; kg += 2) {
+                    group(kg, x0, x1);
+                    group(kg + 1, x1, x0);
+                }
+            } else {
+#pragma unroll 1
+                for (int kg = 0; kg < NGE; kg += 2) {
+                    group(kg, x0, x1);
+                    group(kg + 1, x1, x0);
+                }
             }
             }   // (!EW)
             const int fbase = 16 * half * TPWC + 4 * q;
@@ -469,34 +576,66 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
 #pragma unroll
     for (int c = 0; c < TPWA; ++c) accA[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
     int seg_cnt[3] = {0, 0, 0};
-    if (!WB && !ROWS && A.part == nullptr) {
+    const bool gemmA = !WB && !ROWS && A.part == nullptr;
+    if constexpr (!WB && !ROWS) {
+    if (gemmA) {   // (the GEMM form of stage A exists in fp32 only)
         const float *xa = A.x + mm * A.ldx;
         const int ngA = (A.KA + 15) >> 4;
-        f32x4 wr[S::PA];
-        tc_load<S::PA, NTPA>(wr, A.wA, 0, tid);  // (the GEMM form of stage A exists in fp32 only)
+        tc_load<S::PA, NTPA>(wr, A.wA, 0, tid);
         int kk = 4 * q < A.KA ? 4 * q : A.KA - 4;  // clamped into the row; out-of-range groups are zeroed below
         f32x4 xr = *reinterpret_cast<const f32x4 *>(xa + kk);
-#pragma unroll 1
-        for (int kg = 0; kg < ngA; ++kg) {
-            const f32x4 bv = (16 * kg + 4 * q < A.KA) ? xr : (f32x4){0.f, 0.f, 0.f, 0.f};
-            f32x4 *lw = lds + buf * S::SLAB;
-            tc_store<S::PA>(wr, lw, tid);
-            __syncthreads();
-            if (kg + 1 < ngA) {  // next k-group's operands fly while this one's MFMAs run
-                tc_load<S::PA, NTPA>(wr, A.wA, kg + 1, tid);
+        tc_store<S::PA>(wr, slabs + buf * S::SLAB, tid);
+        if (ngA > 1) tc_load<S::PA, NTPA>(wr, A.wA, 1, tid);
+        else tc_load<S::PB, NTPB>(wr, A.wB, 0, tid);
+        TC_PIN();
+        __syncthreads();
+        // (the last two weight steps are stage B's first two; the input group of the next k-group is requested in
+        //  front of the step's weights, so its wait leaves them in flight)
+        f32x4 x1 = (f32x4){0.f, 0.f, 0.f, 0.f};   // (two registers take turns: see the r_e loops)
+        auto group = [&](int kg, const f32x4 &xc, f32x4 &xn) __attribute__((always_inline)) {
+            const f32x4 bv = (16 * kg + 4 * q < A.KA) ? xc : (f32x4){0.f, 0.f, 0.f, 0.f};
+            const f32x4 *lw = slabs + buf * S::SLAB;
+            f32x4 *nw = slabs + (buf ^ 1) * S::SLAB;
+            tc_mfma<TPWA>(accA, lw + (half * TPWA) * 64 + lane, bv, true, [&]() __attribute__((always_inline)) {
+                if (kg + 1 < ngA) tc_store<S::PA>(wr, nw, tid);
+                else tc_store<S::PB>(wr, nw, tid);
                 kk = 16 * (kg + 1) + 4 * q;
                 kk = kk < A.KA ? kk : A.KA - 4;
-                xr = *reinterpret_cast<const f32x4 *>(xa + kk);
-            }
-            tc_mfma<TPWA>(accA, lw + (half * TPWA) * 64 + lane, bv);
+                xn = *reinterpret_cast<const f32x4 *>(xa + kk);
+                if (kg + 2 < ngA) tc_load<S::PA, NTPA>(wr, A.wA, kg + 2, tid);
+                else tc_load<S::PB, NTPB>(wr, A.wB, kg + 2 - ngA, tid);
+            });
+            TC_PIN();
             buf ^= 1;
+            tc_kgroup_barrier();
+        };
+        int kg = 0;
+#pragma unroll 1
+        for (; kg + 1 < ngA; kg += 2) {
+            group(kg, xr, x1);
+            group(kg + 1, x1, xr);
         }
+        if (kg < ngA) group(kg, xr, x1);
     }
-    WT wrB[S::PB];
-    tc_load<S::PB, NTPB>(wrB, A.wB, 0, tid);  // stage B's first weights fly during the epilogue
+    }
+    // stage B's first weights: behind stage E and behind the GEMM form of stage A the stream has brought them; the
+    // other forms request them here, to fly during whatever stage A is, and store them (tc_b_start) where stage A is
+    // done -- the second stage then flies during the LayerNorm, or while the rows arrive
+    if constexpr (!EW) {
+        if (!gemmA) tc_load<S::PB, NTPB>(wr, A.wB, 0, tid);
+    }
+    auto tc_b_start = [&]() __attribute__((always_inline)) {
+        tc_store<S::PB>(wr, slabs + buf * S::SLAB, tid);
+        tc_load<S::PB, NTPB>(wr, A.wB, 1, tid);
+        TC_PIN();
+    };
     if constexpr (ROWS) {
         const int fbase = 16 * half * TPWA + 4 * q;
-        if constexpr (!EW) tc_rows_request();
+        if constexpr (!EW) {
+            tc_rows_request();
+            TC_PIN();
+            tc_b_start();   // (waits for the weights alone: the rows stay in flight)
+        }
 #pragma unroll
         for (int c = 0; c < TPWA; ++c) accA[c] = fbase + 16 * c < A.NA ? rowv[c] : (f32x4){0.f, 0.f, 0.f, 0.f};
     } else if (A.part == nullptr) {
@@ -593,7 +732,10 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     }
     {
         const int fbase = 16 * half * TPWA + 4 * q;
-        if constexpr (!ROWS) tc_layernorm<TPWA>(accA, fbase, A.NA, A.lnA_g, A.lnA_b, half, q, my_x, peer_x, false);
+        if constexpr (!ROWS) {
+            if (!gemmA) tc_b_start();
+            tc_layernorm<TPWA>(accA, fbase, A.NA, A.lnA_g, A.lnA_b, half, q, my_x, peer_x, false);
+        }
 #pragma unroll
         for (int c = 0; c < TPWA; ++c) my_hid[(half * TPWA + c) * 64] = accA[c];
     }
@@ -603,6 +745,8 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
     f32x4 accB[TPWB];
 #pragma unroll
     for (int c = 0; c < TPWB; ++c) accB[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float *rer = EW ? nullptr : A.re + mm * A.ldre + 4 * q;
+    f32x4 xr = (f32x4){0.f, 0.f, 0.f, 0.f};     // stage C's input group (the form that reads r_e), one k-group ahead
     {
         // the appended k-group: the count features (4 floats per sample) in lane quarter 0, zeros elsewhere
         f32x4 tailv = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -617,23 +761,33 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
                                          : (A.n_counts == 3 ? (f32x4){n0, n1, n0 + n1, 0.f} : (f32x4){n0, 0.f, 0.f, 0.f});
             }
         }
-#pragma unroll
-        for (int kg = 0; kg < NTPA + 1; ++kg) {
-            WT *lw = reinterpret_cast<WT *>(lds) + buf * S::SLAB;
-            tc_store<S::PB>(wrB, lw, tid);
-            __syncthreads();  // (kg == 0: also publishes stage A's hidden tiles)
-            if (kg + 1 < NTPA + 1) tc_load<S::PB, NTPB>(wrB, A.wB, kg + 1, tid);
+        constexpr int NKB = NTPA + 1;   // stage B's k-groups
+        constexpr int C0 = EW ? NGE : 0;   // (stage E form: C's r_e k-groups are done, the r_p groups follow)
+        static_assert(NKB >= 2 && NTB >= 2, "a stage's last two weight steps are the next stage's first two");
+        __syncthreads();  // publishes stage A's hidden tiles and stage B's first weights
+        // (the last two weight steps are stage C's first two)
+        tc_each<NKB>([&](auto KG) __attribute__((always_inline)) {
+            constexpr int kg = decltype(KG)::value;
+            const WT *lw = slabs + buf * S::SLAB;
+            WT *nw = slabs + (buf ^ 1) * S::SLAB;
             const f32x4 bv = kg < NTPA ? my_hid[(kg < NTPA ? kg : 0) * 64] : tailv;
             // (NTB odd: tile NTPB - 1, the second wave's last one, is padding -- its accumulators stay 0)
-            tc_mfma<TPWB>(accB, lw + (half * TPWB) * 64 + lane, bv, !((NTB & 1) && half == 1));
+            tc_mfma<TPWB>(accB, lw + (half * TPWB) * 64 + lane, bv, !((NTB & 1) && half == 1),
+                          [&]() __attribute__((always_inline)) {
+                if constexpr (kg + 1 < NKB) tc_store<S::PB>(wr, nw, tid);
+                else tc_store<S::PC>(wr, nw, tid);
+                if constexpr (kg + 2 < NKB) tc_load<S::PB, NTPB>(wr, A.wB, kg + 2, tid);
+                else {
+                    if constexpr (kg + 2 == NKB) tc_load<S::PC, NTPC>(wr, A.wC, C0, tid);
+                    else tc_load<S::PC, NTPC>(wr, A.wC, C0 + 1, tid);
+                }
+            });
+            TC_PIN();
             buf ^= 1;
-        }
+            if constexpr (kg + 1 < NKB) tc_kgroup_barrier();   // (behind the last k-group the LayerNorm's barriers follow)
+        });
     }
     TC_STAMP(2);
-    WT wrC[S::PC];
-    tc_load<S::PC, NTPC>(wrC, A.wC, EW ? NGE : 0, tid);   // (stage E form: C's r_e k-groups are done, the r_p groups follow)
-    const float *rer = EW ? nullptr : A.re + mm * A.ldre + 4 * q;
-    f32x4 xr = (f32x4){0.f, 0.f, 0.f, 0.f};
     if constexpr (!EW) xr = *reinterpret_cast<const f32x4 *>(rer);  // stage C's first input group
     {
         const int fbase = 16 * half * TPWB + 4 * q;
@@ -647,33 +801,56 @@ __global__ __launch_bounds__(TC_THREADS, NTC >= 32 ? 2 : (TC_THREADS >= 512 ? 4 
 
     TC_STAMP(3);
     // ------------------------------------------------------------------ stage C: folded score head
+    __syncthreads();  // publishes stage B's hidden tiles and the weight stage stored under stage B's last k-group
     if constexpr (!EW) {
 #pragma unroll
     for (int c = 0; c < TPWC; ++c) accC[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-    for (int kg = 0; kg < NGE; ++kg) {  // r_e, read from global memory
-        const f32x4 bv = xr;
-        WT *lw = reinterpret_cast<WT *>(lds) + buf * S::SLAB;
-        tc_store<S::PC>(wrC, lw, tid);
-        __syncthreads();
-        tc_load<S::PC, NTPC>(wrC, A.wC, kg + 1, tid);  // (stage NGE exists: the r_p groups follow)
-        if (kg + 1 < NGE) xr = *reinterpret_cast<const f32x4 *>(rer + 16 * (kg + 1));
-        tc_mfma<TPWC>(accC, lw + (half * TPWC) * 64 + lane, bv);
+    // r_e, read from global memory one k-group ahead, in front of the step's weights; two registers take turns.
+    // (What was requested in front of the LayerNorm has long arrived: said once here, the waits of a loop that stays
+    //  rolled are counted for what the loop itself requests -- not for everything, as its entry would have it.)
+    __builtin_amdgcn_s_waitcnt(0x0f70);
+    f32x4 x1 = (f32x4){0.f, 0.f, 0.f, 0.f};
+    auto group = [&](int kg, const f32x4 &xc, f32x4 &xn) __attribute__((always_inline)) {
+        const WT *lw = slabs + buf * S::SLAB;
+        WT *nw = slabs + (buf ^ 1) * S::SLAB;
+        tc_mfma<TPWC>(accC, lw + (half * TPWC) * 64 + lane, xc, true, [&]() __attribute__((always_inline)) {
+            tc_store<S::PC>(wr, nw, tid);
+            xn = *reinterpret_cast<const f32x4 *>(rer + 16 * (kg + 1 < NGE ? kg + 1 : NGE - 1));
+            tc_load<S::PC, NTPC>(wr, A.wC, kg + 2, tid);  // (stages NGE and NGE + 1 exist: the r_p groups follow)
+        });
+        TC_PIN();
         buf ^= 1;
+        tc_kgroup_barrier();
+    };
+    static_assert(NGE % 2 == 0, "k-groups in pairs");
+    if constexpr (NGE == 8) {   // (D = 128: unrolled, every wait is counted for its own k-group)
+#pragma unroll
+        for (int kg = 0; kg < NGE; kg += 2) {
+            group(kg, xr, x1);
+            group(kg + 1, x1, xr);
+        }
+    } else {
+#pragma unroll 1
+        for (int kg = 0; kg < NGE; kg += 2) {
+            group(kg, xr, x1);
+            group(kg + 1, x1, xr);
+        }
     }
     TC_STAMP(4);
     }
-#pragma unroll
-    for (int kg = 0; kg < NTB; ++kg) {  // r_p, straight from LDS (its padding tile, all zeros, is no k-group worth running)
-        WT *lw = reinterpret_cast<WT *>(lds) + buf * S::SLAB;
-        tc_store<S::PC>(wrC, lw, tid);
-        __syncthreads();  // (kg == 0: also publishes stage B's hidden tiles)
-        if (kg + 1 < NTB) tc_load<S::PC, NTPC>(wrC, A.wC, NGE + kg + 1, tid);
-        TC_PIN();
-        tc_mfma<TPWC>(accC, lw + (half * TPWC) * 64 + lane, my_hid[kg * 64]);
+    // r_p, straight from LDS (its padding tile, all zeros, is no k-group worth running)
+    tc_each<NTB>([&](auto KG) __attribute__((always_inline)) {
+        constexpr int kg = decltype(KG)::value;
+        const WT *lw = slabs + buf * S::SLAB;
+        WT *nw = slabs + (buf ^ 1) * S::SLAB;
+        tc_mfma<TPWC>(accC, lw + (half * TPWC) * 64 + lane, my_hid[kg * 64], true, [&]() __attribute__((always_inline)) {
+            if constexpr (kg + 1 < NTB) tc_store<S::PC>(wr, nw, tid);
+            if constexpr (kg + 2 < NTB) tc_load<S::PC, NTPC>(wr, A.wC, NGE + kg + 2, tid);
+        });
         TC_PIN();
         buf ^= 1;
-    }
+        if constexpr (kg + 1 < NTB) tc_kgroup_barrier();
+    });
     TC_STAMP(5);
     {
         const int fbase = 16 * half * TPWC + 4 * q;

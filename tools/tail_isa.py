@@ -12,7 +12,13 @@ runs it: unconditional branches and backward conditional branches (loops) are ta
 vmcnt counts vector memory operations in issue order: ``vmcnt(N)`` covers a load once at most N others were issued behind
 it.
 
-    python tools/tail_isa.py [--json] [--source FILE] [--extra "-D..."]
+``kloops()`` reads the order of a k-group back: what stands between a k-group's last ``v_mfma`` and the barrier that ends
+it (``tc_kgroup_barrier``) -- the design wants nothing but the wait for the LDS counter there: the weight stream's store,
+its wait for the weights and the next request run among the k-group's MFMAs --, the wait that covers stage B's first
+request (``tc_load(.., A.wB, 0, ..)``), and whether a load of stage A's rows (``tc_rows_request``) is issued in front of
+the first store of stage C's weights, whose wait it would lengthen (vmcnt counts in issue order).
+
+    python tools/tail_isa.py [--json] [--kloops] [--source FILE] [--extra "-D..."]
 """
 import argparse
 import json
@@ -66,6 +72,124 @@ def source_sites(path):
     if body is None:
         raise RuntimeError("no tc_load in %s" % path)
     return sites, body
+
+
+def _body(lines, pattern, close):
+    """(first, last) line of the definition whose first line matches `pattern`, closed by a line starting with `close`"""
+    for i, text in enumerate(lines, 1):
+        if re.search(pattern, text):
+            j = i
+            while not lines[j - 1].startswith(close) or j == i and "{" in text and "}" not in text:
+                j += 1
+            return (i, j)
+    return None
+
+
+def source_marks(path):
+    """line ranges of tc_kgroup_barrier, tc_rows_request and tc_store, and {line: stage expression} of the tc_load calls"""
+    lines = open(path).read().split("\n")
+    exprs = {}
+    for i, text in enumerate(lines, 1):
+        m = re.search(r"\btc_load<[^;]*?>\(\w+,\s*A\.w([A-Z])\w*,\s*([^;]*?),\s*tid\)", text)
+        if m:
+            exprs[i] = (m.group(1), m.group(2).strip())
+    one = next(i for i, t in enumerate(lines, 1) if re.search(r"\bvoid tc_kgroup_barrier\(", t))
+    return {"barrier": (one, one), "rows": _body(lines, r"auto tc_rows_request = ", "    };"),
+            "store": _body(lines, r"\bvoid tc_store\(", "}"), "exprs": exprs}
+
+
+def _inside(loc, src_name, rng):
+    return any(f == src_name and rng[0] <= l <= rng[1] for f, l in loc)
+
+
+def covering_wait(k, start):
+    """(index, v_mfma in between, N) of the ``s_waitcnt vmcnt(N)`` that covers the load at `start`, walked as walk() does"""
+    ins, labels = k["ins"], k["labels"]
+    behind, mfma, i, taken = 0, 0, start + 1, set()
+    for _ in range(MAX_WALK):
+        if i >= len(ins):
+            return None
+        op, rest, _loc = ins[i]
+        if op.startswith("v_mfma"):
+            mfma += 1
+        elif is_vmem(op):
+            behind += 1
+        elif op == "s_waitcnt":
+            m = _VMCNT.search(rest)
+            if m and int(m.group(1)) <= behind:
+                return i, mfma, int(m.group(1))
+        elif op == "s_endpgm":
+            return None
+        elif op == "s_branch":
+            i = labels[rest.strip()]
+            continue
+        elif op.startswith("s_cbranch"):
+            tgt = labels.get(rest.strip())
+            if tgt is not None and tgt <= i and (i, tgt) not in taken:
+                taken.add((i, tgt))
+                i = tgt
+                continue
+        i += 1
+    return None
+
+
+def kloops(source=None, extra=(), hipcc=None):
+    """per kernel: {"kernel", "kgroup_ends": [[what stands between the last v_mfma and a k-group's barrier], ..],
+    "b_first": [{"mfma_to_wait"}] for the loads of tc_load(.., A.wB, 0, ..), "c_first_store": {"rows_in_front": row loads
+    issued in front of the first store of stage C's weights, "left_in_flight": N of the wait in front of that store}}"""
+    hipcc = hipcc or find_hipcc()
+    if not hipcc:
+        raise RuntimeError("hipcc not found")
+    src = os.path.abspath(source or os.path.join(CSRC, "tail_chain.hip"))
+    name = os.path.basename(src)
+    marks = source_marks(src)
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "tail_chain.s")
+        _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-gline-tables-only", "-S", "-I", CSRC,
+              "-I", os.path.join(ROOT, "include")] + list(extra) + [src, "-o", out], CSRC)
+        kernels, _meta = parse_kernels(open(out).read())
+    res = []
+    for k in kernels:
+        ins = k["ins"]
+        ends = []
+        for i, (op, _rest, loc) in enumerate(ins):
+            if op != "s_barrier" or not _inside(loc, name, marks["barrier"]):
+                continue
+            between, j = [], i - 1
+            while j >= 0 and not ins[j][0].startswith("v_mfma"):
+                between.append(("%s %s" % (ins[j][0], ins[j][1].strip())).strip())
+                j -= 1
+            ends.append(between[::-1])
+        def site(loc):      # the tc_load call that made a load: (stage, expression) or None
+            for (_f0, _l0), (f1, l1) in zip(loc, loc[1:]):
+                if f1 == name and l1 in marks["exprs"]:
+                    return marks["exprs"][l1]
+            return None
+        b_first, c_loads = [], []
+        for i, (op, _rest, loc) in enumerate(ins):
+            if not op.startswith("global_load"):
+                continue
+            st = site(loc)
+            if st == ("B", "0"):
+                w = covering_wait(k, i)
+                b_first.append({"mfma_to_wait": w[1] if w else None})
+            elif st and st[0] == "C":
+                c_loads.append(i)
+        c_store = None
+        if c_loads and marks["rows"]:
+            w = covering_wait(k, c_loads[0])
+            if w:
+                st_i = next((j for j in range(w[0], len(ins)) if ins[j][0].startswith("ds_write") and
+                             _inside(ins[j][2], name, marks["store"])), None)
+                if st_i is not None:
+                    rows = sum(1 for j in range(st_i) if ins[j][0].startswith("global_load") and
+                               _inside(ins[j][2], name, marks["rows"]))
+                    c_store = {"rows_in_front": rows, "left_in_flight": w[2]}
+        nta, ntb, ntc, wm, rows_, ew = k["targs"]
+        res.append({"kernel": "tail_chain_kernel<%d,%d,%d,%d,%s,%s>" % (nta, ntb, ntc, wm, "true" if rows_ else "false",
+                                                                         "true" if ew else "false"),
+                    "kgroup_ends": ends, "b_first": b_first, "c_first_store": c_store})
+    return res
 
 
 def lds_bytes(hipcc, src, shapes, extra, tmp):
@@ -230,9 +354,24 @@ def report(res):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--kloops", action="store_true", help="the order of the k-groups instead (kloops())")
     ap.add_argument("--source", default=None, help="another copy of tail_chain.hip (say, the parent commit's)")
     ap.add_argument("--extra", default="", help="further compiler flags")
     a = ap.parse_args()
+    if a.kloops:
+        res = kloops(a.source, a.extra.split())
+        if a.json:
+            print(json.dumps(res))
+            return
+        for k in res:
+            odd = [e for e in k["kgroup_ends"] if any(not x.startswith("s_waitcnt lgkmcnt") for x in e)]
+            print("%s  k-group barriers %d, with more than the LDS wait in front: %d  stage B's first request: %s  "
+                  "first store of stage C's weights: %s" %
+                  (k["kernel"], len(k["kgroup_ends"]), len(odd), [b["mfma_to_wait"] for b in k["b_first"]],
+                   k["c_first_store"]))
+            for e in odd[:4]:
+                print("     " + " | ".join(e))
+        return
     res = run(a.source, a.extra.split())
     print(json.dumps(res) if a.json else report(res))
 
