@@ -1299,6 +1299,63 @@ int lpf_node_triangles(int64_t n, int64_t nnz, const int64_t *rowptr, const int3
                        int32_t split_threshold, int32_t *scratch, int64_t *triangles, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Louvain communities (community.hip; lpformer_amd/community.py): one round of local moves on a level
+ * graph and the inside weight of a labelling -- the level between a node's neighbourhood and its connected component.
+ * The reference has no such code.  The three symbols were added within ABI 16: the addition changes no existing symbol,
+ * so LPF_ABI_VERSION stays.
+ *
+ * Level graph.  A CSR with sorted, unique int32 columns and a SYMMETRIC pattern, as in the section above: u ~ v iff
+ * u != v and v is in row u; every kernel skips col == row.  weight int64[nnz] gives w(u, v) per stored entry (NULL: all
+ * 1, level 0).  k int64[n]: k[v] = sum_{u != v} w(v, u) + s[v], s the caller's self weight (the inside weight of the
+ * community a coarse node stands for; level 0: all 0).  two_m = sum_v k[v], the same at every level; two_m < 2^31, so
+ * every k, tot and w_C is below 2^31 and every product below is below 2^62.  Integers only; a pure function of its
+ * arguments (not of the launch shape or of timing); no workgroup waits on another; nothing is read back.  Common
+ * limits (LPF_ERR_INVALID otherwise, before any launch): 0 <= n < 2^31 - 1, 0 <= nnz < 2^31 - 1, no NULL array (col /
+ * row / comm of lpf_community_quality may be NULL when nnz == 0, weight always).  Row pointers outside [0, nnz] read
+ * as an empty row; a column or a community outside [0, n) is skipped before it indexes.
+ * ---------------------------------------------------------------------------------------------- */
+/* Rows longer than this are the caller's to list for lpf_community_move (a 256-thread workgroup each); shorter ones
+ * share a wavefront, eight lanes per row. */
+#define LPF_COMM_LONG_ROW 64
+/* Slots of the LDS table of a listed row (lds_slots): the default, and the most a workgroup's LDS holds (12 bytes per
+ * slot: 48 KiB and 96 KiB of the 160 KiB). */
+#define LPF_COMM_LDS_SLOTS 4096
+#define LPF_COMM_LDS_SLOTS_MAX 8192
+/* ONE round of local moves.  Reads the accepted state -- comm int32[n] (community ids are node ids of the level), tot
+ * int64[n] (tot[c] = sum of k over the members of c), cnt int32[n] (members of c) -- and writes new_comm int32[n]:
+ * the round is double-buffered.  Node v is ACTIVE iff the top bit of
+ *     lpf_mix64(lpf_draw_key(seed, ((uint64_t)level << 32) + round) + G (v + 1))
+ * is set (the draw of the negatives section above); an inactive node keeps comm[v].  An active node with cur = comm[v]
+ * visits every community C among its neighbours' communities, w_C = sum_{u ~ v, comm[u] = C} w(v, u):
+ *     gain(C) = two_m w_C - k_v (tot_C - [C == cur] k_v),      stay = gain(cur)  (w_cur = 0 with no neighbour in cur).
+ * A candidate is a C != cur with gain(C) > stay, unless cnt[cur] == 1 && cnt[C] == 1 && C > cur (two singletons may
+ * not swap).  The candidate of the largest gain wins, ties to the smaller id; without a candidate v stays.  *moved
+ * (one int32, NOT zeroed here) counts the nodes with new_comm[v] != comm[v]: one integer atomic per wavefront at most.
+ *
+ * long_rows int32[n_long]: every row of more than LPF_COMM_LONG_ROW entries, each once (a row that is missing is never
+ * written).  They are handled by min(n_long, 512) persistent workgroups that stride the list; a row of len entries
+ * aggregates its (community, weight) pairs in an open-addressing table of T = max(64, 2^ceil(log2(2 len))) slots
+ * (int32 keys claimed by compare-and-swap, int64 sums by 64-bit integer adds, at most T probes), in LDS where
+ * T <= lds_slots -- a power of two in [64, LPF_COMM_LDS_SLOTS_MAX], LPF_ERR_INVALID otherwise -- and else in the
+ * workgroup's region of scratch: lpf_community_workspace_bytes(n_long, longest row, lds_slots) bytes of device memory
+ * (0: none needed, scratch may be NULL), ALL ZERO on entry and left all zero.  scratch_bytes is what the caller
+ * passed; a row whose table neither LDS nor its region holds keeps its community.  A small lds_slots exists so that
+ * tests reach the device-memory table with rows of a few hundred entries; the result is the same for every value. */
+int64_t lpf_community_workspace_bytes(int64_t n_long, int64_t max_row, int32_t lds_slots);
+int lpf_community_move(int64_t n, int64_t nnz, const int64_t *rowptr, const int32_t *col, const int64_t *weight,
+                       const int64_t *k, const int32_t *comm, const int64_t *tot, const int32_t *cnt, int64_t two_m,
+                       uint64_t seed, int32_t level, int32_t round, const int32_t *long_rows, int64_t n_long,
+                       int32_t lds_slots, void *scratch, int64_t scratch_bytes, int32_t *new_comm, int32_t *moved,
+                       void *stream);
+/* *inside (one int64, zeroed here) = the sum of w over the stored entries (row[e], col[e]) -- row int32[nnz] is the
+ * row id of every entry -- with row != col and comm[row] == comm[col]: both directions of every inside edge.  comm may
+ * hold ANY int32 labels.  Entry-parallel: at most 1,024 workgroups stride the entries, a wavefront and a workgroup
+ * reduction, one 64-bit integer atomic per workgroup at most (every add lands on this one word).
+ * The modularity numerator of the labelling is two_m (inside + sum_v s[v]) - sum_c tot_c^2. */
+int lpf_community_quality(int64_t n, int64_t nnz, const int32_t *row, const int32_t *col, const int64_t *weight,
+                          const int32_t *comm, int64_t *inside, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host side (liblpformer_host.so)
  * ---------------------------------------------------------------------------------------------- */
 

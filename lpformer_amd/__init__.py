@@ -21,6 +21,12 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
                                         (clustering, component_size, summary), pair_node_values / same_component (the
                                         per-pair axis for metrics_by_bin), DEGREE_BINS, CORE_BINS, structure_reference
                                         (numpy / scipy restatement)
+    communities                         Louvain communities of the typing adjacency (device move rounds: short rows in
+                                        registers, hub rows through an LDS hash table; exact integers, a pure function
+                                        of graph and seed): Communities (label = smallest id, size, hierarchy, summary),
+                                        same_community / COMMUNITY_BINS (intra- or inter-community, for metrics_by_bin),
+                                        partition_quality (exact modularity numerator of any labelling),
+                                        communities_reference (numpy restatement)
     recommend                           top-K new links per source node (device candidates, scoring, top-K)
     similar_nodes                      the m nodes nearest to each query by inner product or cosine over the encoder's
                                         output, the raw features or any table (device matrix-core kernel with the top-m
@@ -46,6 +52,8 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
 from . import evaluate, graph, mask_delta, readers  # noqa: F401
 from .bootstrap import (bootstrap_by_bin, bootstrap_metrics, bootstrap_sums, bootstrap_sums_reference,  # noqa: F401
                         compare_metrics)
+from .community import (COMMUNITY_BINS, Communities, communities, communities_reference,  # noqa: F401
+                        partition_quality, same_community)
 from .data import link_split  # noqa: F401
 from .distance import DIST_BINS, pair_distance  # noqa: F401
 from .epoch import TrainEdges, fit, train_epoch  # noqa: F401
@@ -77,4 +85,5 @@ __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_
            "negatives_reference", "link_split", "pair_hop_counts", "hop_counts_reference", "elph_features",
            "ball_jaccard", "bootstrap_sums", "bootstrap_sums_reference", "bootstrap_metrics", "compare_metrics",
            "bootstrap_by_bin", "similar_nodes", "similar_reference", "Similar", "node_structure", "NodeStructure",
-           "structure_reference", "pair_node_values", "same_component", "DEGREE_BINS", "CORE_BINS"]
+           "structure_reference", "pair_node_values", "same_component", "DEGREE_BINS", "CORE_BINS", "communities",
+           "Communities", "communities_reference", "partition_quality", "same_community", "COMMUNITY_BINS"]
