@@ -18,6 +18,10 @@ row's scale) rather than relative to the element.  Each flagged element is charg
 output through the absolute values of the downstream coefficients (``ln_bound`` for a LayerNorm, 1-Lipschitz ReLUs):
 that is the ``flip`` bound every function returns next to its result.  A perturbation already carried into a value is
 added to its flagging window and to its charge, so roundings further down that it may tip are covered as well.
+Where a value's fp32 error is not of that form the caller widens the window: h_e by the conditioning of the closed-form
+PE variance (``attention_ref(h_window=...)``), the tail's activations by the rounding of the bias add in front of their
+LayerNorm (``bias_add_window``).  The charge of h_e goes through the softmax in a form that holds for any size of the
+score change (``attention_ref``), proved by perturbation in tests/test_bf16_reference_host.py.
 """
 from __future__ import annotations
 
@@ -109,6 +113,16 @@ def ln_bound(dx, xhat, sd, g):
                               np.abs(xhat) * (np.abs(xhat) * dx).mean(axis=-1, keepdims=True))
 
 
+def bias_add_window(v, xhat, sd, g, unit=U32):
+    """|dy| of y = LayerNorm(v) from the one fp32 rounding of every element of v as the bias is added to the finished
+    product (the kernels' epilogues: tail_chain.hip, dense_chain.hip): |dv| <= unit |v| for the element itself, a hard
+    bound; through the row's mean and variance the n roundings are independent and add in quadrature."""
+    dv = unit * np.abs(v)
+    n = v.shape[-1]
+    return np.abs(g) / sd * (dv + np.sqrt((dv * dv).mean(axis=-1, keepdims=True) / n) +
+                             np.abs(xhat) * np.sqrt((xhat * xhat * dv * dv).mean(axis=-1, keepdims=True) / n))
+
+
 def row_floor(x, k: int):
     """The absolute floor of the flag window of a LayerNorm output: row RMS / sqrt(K)."""
     return np.sqrt((x * x).mean(axis=-1, keepdims=True)) / np.sqrt(k)
@@ -139,7 +153,8 @@ H_TERMS = 16   # fp32 operations behind an element of h_e: 3-term u, 6-term vari
 
 
 def attention_ref(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, round_z=False, round_h=False, round_wfold=False,
-                  drop=None, rounder=rne_bf16, ln_eps=LN_EPS, detail=False):
+                  drop=None, rounder=rne_bf16, ln_eps=LN_EPS, detail=False, h_window=None, flagged_to=None,
+                  factor=False):
     """LinkAttention + post_att_norm on the folded tables:  k_e = Z[v] + Wfold_t h_e + bfold_t,  s_e = att .
     LeakyReLU_0.2(k_e * q[pair]),  PyG softmax per pair (max-shifted, + 1e-16), out = sum_e alpha_e k_e + bias -> LN.
 
@@ -147,7 +162,23 @@ def attention_ref(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, round_z=False, roun
     (numpy or tensors: wfold, bfold, att, pe_tab, pe_stat).  ``drop``: (type, entry) left out (near-miss of a kernel
     that loses one entry).  Returns dict pre, post, counts [bs, 3], and the flip bound ``d_post`` of ``round_h``
     (h_e is rounded inside the kernel) with its flag statistics.  ``ln_eps``: the epsilon of post_att_norm (near-miss:
-    0).  ``detail``: also ``ent``, the per-entry quantities (pair, type, node, h, k, score, alpha) in type order."""
+    0).  ``detail``: also ``ent``, the per-entry quantities (pair, type, node, h, k, score, alpha) in type order.
+    ``h_window``: per type an absolute window [E_t, D] (or None) added to the flag window of h_e -- the fp32 error of
+    h_e beyond H_TERMS 2^-24 mag, f32_error_model.h_bound: the conditioning of the closed-form variance.
+    ``factor``: the variance of the PE LayerNorm as the sum of squares of the moment matrix's triangular factor (rows
+    3-5 of ``pe_stat``), which is what the kernels evaluate, instead of the six moments written out (rows 0-2): the
+    same function of the exact tables, but where the form cancels (kappa large) the fp32 STORAGE of the six moments
+    alone moves h_e by u kappa, 1e-4 ... 3e-4 under ``pe_diff_big`` -- far outside the flag window.
+    ``flagged_to``: "up", "down" or a numpy Generator -- every FLAGGED element of h_e goes to its upper / lower / a
+    randomly chosen bf16 neighbour instead of the nearest (the perturbation the flip bound ``d_post`` has to cover).
+
+    The flip bound holds for any size of the score change.  Flagged elements move k_e by at most dk_e and s_e by at
+    most ds_e; the pair's weights become alpha'_e = alpha_e exp(+-ds_e) / Z, Z = sum_f alpha_f exp(+-ds_f), so
+    |log Z| <= L = max(log(1 + sum_f alpha_f (e^ds_f - 1)), -log(1 - sum_f alpha_f (1 - e^-ds_f))) and
+    |alpha'_e / alpha_e - 1| <= exp(ds_e + L) - 1 for EVERY entry of the pair (ds_e = 0 where nothing is flagged).  With
+    out' - out = sum_e alpha'_e dk_e + sum_e (alpha'_e - alpha_e) (k_e - out):
+        d_pre = sum_e alpha_e (exp(ds_e + L) dk_e + (exp(ds_e + L) - 1) |k_e - out|).
+    ``ds_max``: the largest ds_e (0 without flags)."""
     z, q = _f64(z), _f64(q)
     wfold, bfold, att = _f64(w["wfold"]), _f64(w["bfold"]), _f64(w["att"])
     tab, stat = _f64(w["pe_tab"]), _f64(w["pe_stat"])
@@ -169,10 +200,20 @@ def attention_ref(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, round_z=False, roun
             keep[drop[1]] = False
         pair, node, pa, pb = pair[keep], node[keep], pa[keep], pb[keep]
         counts[:, t] = np.bincount(pair, minlength=bs)[:bs]
-        h, mag = pe_hidden(tab[t], stat[t], pa, pb)
+        h, mag = pe_hidden(tab[t], stat[3 + t], pa, pb, factor=True) if factor else pe_hidden(tab[t], stat[t], pa, pb)
         ch = np.zeros_like(h)
         if round_h:
-            h, fl, ch = rounded(h, H_TERMS * U32 * mag, rounder)
+            win = H_TERMS * U32 * mag
+            if h_window is not None and h_window[t] is not None:
+                win = win + _f64(h_window[t])[keep]
+            h0 = h
+            h, fl, ch = rounded(h0, win, rounder)
+            if flagged_to is not None:
+                sp = bf16_spacing(h0)
+                lo, hi = np.floor(h0 / sp) * sp, np.ceil(h0 / sp) * sp
+                to = hi if flagged_to == "up" else lo if flagged_to == "down" else \
+                    np.where(flagged_to.random(h0.shape) < 0.5, hi, lo)
+                h = np.where(fl, to, h)
             n_flag += int(fl.sum())
             n_elem += fl.size
         keys.append(z[node] + h @ wfold[t].T + bfold[t])
@@ -184,6 +225,7 @@ def attention_ref(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, round_z=False, roun
     pre = np.zeros((bs, d))
     d_pre = np.zeros((bs, d))
     ent = None
+    ds_max = 0.0
     if pairs:
         pair = np.concatenate(pairs)
         k = np.concatenate(keys)
@@ -204,8 +246,8 @@ def attention_ref(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, round_z=False, roun
                    "score": score, "alpha": alpha}
         hit = np.flatnonzero(ch.any(axis=1))
         if hit.size:
-            # one flipped h element moves k_e by Wfold[:, k] delta and s_e by (att q) . Wfold[:, k] delta; the output
-            # moves by alpha_e (dk_e + (k_e - out) ds_e)
+            # one flipped h element moves k_e by Wfold[:, k] delta and s_e by (att q) . Wfold[:, k] delta (LeakyReLU is
+            # 1-Lipschitz); the weights and the output follow as the docstring says, for any size of ds_e
             dk = np.zeros((hit.size, d))
             ds = np.zeros(hit.size)
             for t in range(3):
@@ -215,12 +257,21 @@ def attention_ref(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, round_z=False, roun
                     dk[m] = ch[hit[m]] @ wa.T
                     ds[m] = ((np.abs(att * qe[hit[m]]) @ wa) * ch[hit[m]]).sum(axis=1)
             ph = pair[hit]
-            contrib = alpha[hit, None] * (dk + np.abs(k[hit] - pre[ph]) * ds[:, None])
+            up, dn = np.zeros(bs), np.zeros(bs)
+            np.add.at(up, ph, alpha[hit] * np.expm1(ds))
+            np.add.at(dn, ph, alpha[hit] * -np.expm1(-ds))
+            lz = np.maximum(np.log1p(up), -np.log1p(-np.minimum(dn, 1.0 - 2.0 ** -52)))
+            dev = np.abs(k - pre[pair])
+            np.add.at(d_pre, pair, (alpha * np.expm1(lz)[pair])[:, None] * dev)
+            grow = np.exp(ds + lz[ph])
+            contrib = alpha[hit, None] * (grow[:, None] * dk + (grow - np.exp(lz[ph]))[:, None] * dev[hit])
             np.add.at(d_pre, ph, contrib)
+            ds_max = float(ds.max())
     pre = pre + _f64(att_bias)
     post, xhat, sd = layer_norm(pre, _f64(ln_g), _f64(ln_b), ln_eps)
     d_post = ln_bound(d_pre, xhat, sd, _f64(ln_g))
-    out = {"pre": pre, "post": post, "counts": counts, "d_post": d_post, "n_flag": n_flag, "n_elem": n_elem}
+    out = {"pre": pre, "post": post, "counts": counts, "d_post": d_post, "n_flag": n_flag, "n_elem": n_elem,
+           "d_pre": d_pre, "ds_max": ds_max}
     if detail:
         out["ent"] = ent
     return out
@@ -246,14 +297,20 @@ def elementwise_hidden(x_node, batch, w0, b0, g, b):
 
 
 def tail_ref(rows, feats_cnt, r_e, t, *, round_act=False, round_w=False, lite=None, d_rows=None, rounder=rne_bf16,
-             ln_eps=LN_EPS):
+             ln_eps=LN_EPS, f32_unit=None, win_re=None):
     """pairwise_lin's first layer + LN + ReLU, then the folded score head (``LinkTransformer._score_fold``):
         r_p = ReLU(LN_B(W_p0 [row | counts] + b_p0)),  logit = w_dot . ReLU(A [r_e | r_p] + c) + b_dot.
     t: dict w_p0 [pd, pd], b_p0, lnB_g, lnB_b, A [2D, D + pd], c [2D], w_dot [2D], b_dot, and bC_empty (lite rows).
     ``round_w`` rounds W_p0 and A (the wB / wC images), ``round_act`` the GEMM inputs [row | counts], r_e and r_p.
     ``lite`` (bool [bs]): pairs the tail takes without a pairwise branch -- w_dot . ReLU(A_e r_e + bC_empty) + b_dot
     (lpf_tail_chain_rows_perm_*: a workgroup of pairs without selected nodes).  ``d_rows``: a bound on the rows'
-    error carried in (a bf16 attention upstream).  ``ln_eps``: the epsilon of LN_B (near-miss: 0).  Returns dict logit, r_p, d_logit (flip bound), n_flag, n_elem."""
+    error carried in (a bf16 attention upstream).  ``ln_eps``: the epsilon of LN_B (near-miss: 0).
+    ``f32_unit`` / ``win_re``: the flag windows of r_p and r_e widened (windows only, nothing is charged: the tests'
+    error model holds the fp32 error itself) by ``bias_add_window`` of the pre-activation behind them -- computed here
+    for r_p (``f32_unit`` = 2^-24), given as ``win_re`` [bs, D] for r_e (the elementwise kernel's).
+    K 2^-24 max(|x|, floor) knows nothing of a bias that the LayerNorm removes again (param_regimes' ``ln_offset``: +30
+    on b_p0 and b_e0 -- the pre-activation then carries 30 2^-24 whatever its deviation from the mean is).
+    Returns dict logit, r_p, d_logit (flip bound), n_flag, n_elem."""
     rows, r_e = _f64(rows), _f64(r_e)
     x = np.concatenate([rows, _f64(feats_cnt)], axis=1)
     d = rows.shape[1]
@@ -269,7 +326,10 @@ def tail_ref(rows, feats_cnt, r_e, t, *, round_act=False, round_w=False, lite=No
         win = np.zeros_like(x)
         win[:, :d] = flag_window(rows, d, row_floor(rows, d))     # post-LN rows: D-term products upstream
         x, fl, dx = rounded(x, win, rounder, dx)
-        re_, fl2, dre = rounded(r_e, flag_window(r_e, d, row_floor(r_e, d)), rounder)
+        w_re = flag_window(r_e, d, row_floor(r_e, d))
+        if win_re is not None:
+            w_re = w_re + np.where(r_e > 0.0, _f64(win_re), 0.0)       # (a unit that is off is read as an exact 0)
+        re_, fl2, dre = rounded(r_e, w_re, rounder)
         n_flag += int(fl[:, :d].sum() + fl2.sum())
         n_elem += fl[:, :d].size + fl2.size
     else:
@@ -279,7 +339,10 @@ def tail_ref(rows, feats_cnt, r_e, t, *, round_act=False, round_w=False, lite=No
     r_p = np.maximum(y, 0.0)
     drp = ln_bound(np.abs(dx) @ np.abs(w_p0).T, xhat, sd, _f64(t["lnB_g"]))
     if round_act:
-        rp_, fl3, drp = rounded(r_p, flag_window(r_p, kb, row_floor(r_p, kb)), rounder, drp)
+        w_rp = flag_window(r_p, kb, row_floor(r_p, kb))
+        if f32_unit is not None:     # (a unit that is off is read as an exact 0)
+            w_rp = w_rp + np.where(r_p > 0.0, bias_add_window(v, xhat, sd, _f64(t["lnB_g"]), f32_unit), 0.0)
+        rp_, fl3, drp = rounded(r_p, w_rp, rounder, drp)
         n_flag += int(fl3.sum())
         n_elem += fl3.size
     else:

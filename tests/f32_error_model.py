@@ -140,6 +140,16 @@ def elementwise_bound(x_node, batch, w0, b0, g, b):
     return R.ln_bound(EPS23 * mag, xhat, sd, _f64(g)) + EPS23 * np.maximum(1.0, np.abs(y))
 
 
+def elementwise_window(x_node, batch, w0, b0, g, b):
+    """``bf16_reference.bias_add_window`` of r_e's pre-activation W_e0 (x_a * x_b) + b_e0: what the flag window of a
+    bf16 tail's r_e has to include beside K 2^-24 max(|r_e|, floor) (``tail_ref(win_re=...)``)."""
+    x = _f64(x_node)
+    batch = np.asarray(batch, np.int64)
+    v = (x[batch[0]] * x[batch[1]]) @ _f64(w0).T + _f64(b0)
+    _, xhat, sd = R.layer_norm(v, _f64(g), _f64(b))
+    return R.bias_add_window(v, xhat, sd, _f64(g))
+
+
 def tail_bound(rows, feats_cnt, r_e, t, b_rows, b_re, lite=None):
     """(carried, own), both [bs]: ``carried`` = the rows' bound ``b_rows`` through the tail (tail_ref's d_logit),
     ``own`` = 2^-23 T, the tail's own fp32 error with C_tail = 1.  The logit bound is carried + C_tail own (b_rows
@@ -276,6 +286,50 @@ def conditioning_bound(ref, w, qmag, att_bias, ln_g, ln_b, b_h):
     _, xhat, sd = R.layer_norm(pre, _f64(ln_g), _f64(ln_b))
     b_pre = acc + np.sqrt(sens2)
     return b_pre, R.ln_bound(b_pre, xhat, sd, _f64(ln_g))
+
+
+# ------------------------------------------------------------------------------------------------- bf16 kernels
+# A bf16 attention kernel does the fp32 kernels' arithmetic on rounded inputs (a bf16 x bf16 product is exact in the
+# fp32 accumulator), so it is held to the same per-row model, stated on the restatement with that kernel's roundings
+# on: K_e from the ROUNDED Z (and the rounded Wfold image and the rounded h_e for the matrix-core kernel) -- what the
+# kernel multiplies --, alpha, k_e and the LayerNorm of the rounded reference, the fp32 kernels' constants, plus the
+# restatement's flip bound d_post for the one value a kernel rounds after computing it (h_e, matrix-core kernel):
+#     |got - ref16| <= C_ATT b_post(ref16) + C_H b_post_h(ref16) + d_post.
+def h_window(sel, msd, kappa="root"):
+    """Per type b_h [E_t, D] (``h_bound``, C_H = 1) of a selection, from the fp64 state dict: the fp32 error of h_e
+    that the flag window of ``attention_ref(round_h=True)`` has to include beside H_TERMS 2^-24 mag."""
+    from tests import unfolded_reference as U
+    out = []
+    for t, s in enumerate(sel):
+        if s is None or not len(s[1]):
+            out.append(None)
+            continue
+        h, ru, kap, _ = U.pe_hidden(msd, t, s[1], s[2])
+        ent = {"kappa": kap, "ru0": ru[0][0], "ru1": ru[1][0], "rm0": ru[0][1], "rm1": ru[1][1], "h": h,
+               "type": np.full(h.shape[0], t)}
+        out.append(h_bound(ent, msd, kappa))
+    return out
+
+
+def attention_bf16(sel, z, q, w, att_bias, ln_g, ln_b, bs, *, fused, b_h=None, rounder=R.rne_bf16, round_z=True):
+    """(ref16, bnd) of one bf16 attention kernel: the restatement with Z rounded (``fused``, the matrix-core kernel:
+    the Wfold image and h_e as well, flags within H_TERMS 2^-24 mag + ``b_h``) and the C = 1 bounds on it: b_post,
+    b_post_worst, K, M ... of ``attention_bound`` with the rounded tables, and b_post_h, ``b_h`` carried through
+    ``conditioning_bound`` (zero without ``b_h``).  ``b_h``: ``h_window``'s list.  Z is the fp32 table the kernel's
+    image is cast from.  ``round_z=False`` (with ``fused=False``): nothing is rounded -- an fp32 kernel's reference and
+    bound in the same form."""
+    assert round_z or not fused
+    factor = np.shape(w["pe_stat"])[0] >= 6         # (the factor rows, where the tables have them: the kernels' form)
+    ref = attention(sel, z, q, w, att_bias, ln_g, ln_b, bs, round_z=round_z, round_h=fused, round_wfold=fused,
+                    rounder=rounder, h_window=b_h if fused else None, factor=factor)
+    w16 = {"wfold": rounder(w["wfold"]) if fused else _f64(w["wfold"]), "bfold": _f64(w["bfold"]), "att": _f64(w["att"])}
+    bnd = attention_bound(ref, rounder(z) if round_z else z, w16, q, att_bias, ln_g, ln_b)
+    bnd["b_post_h"] = np.zeros_like(bnd["b_post"])
+    if b_h is not None and ref["ent"] is not None:
+        flat = np.concatenate([b for b in b_h if b is not None])
+        assert flat.shape == ref["ent"]["h"].shape
+        bnd["b_post_h"] = conditioning_bound(ref, w16, np.abs(_f64(q)), att_bias, ln_g, ln_b, flat)[1]
+    return ref, bnd
 
 
 def unfolded_bounds(ref, x_node, batch, msd, ssd, kappa="root"):

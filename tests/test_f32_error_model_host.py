@@ -175,3 +175,27 @@ def test_layer_norm_eps_default_is_bitwise_the_old_result():
     y0 = R.layer_norm(x, g, b, eps=0.0)[0]
     assert not np.array_equal(y0, R.layer_norm(x, g, b)[0])
     assert np.abs(y0 - R.layer_norm(x, g, b)[0]).max() > 1e-3        # (rows of scale 1e-4: the epsilon matters there)
+
+
+@pytest.mark.parametrize("which", ["narrow", "wide"])
+def test_bf16_bound_holds_a_plain_f32_evaluation_on_the_rounded_table(which):
+    """``attention_bf16`` (the per-row bound of a *_zbf16 kernel: the restatement with Z rounded, K_e from the rounded
+    Z): the plain fp32 evaluation on the bf16 image of Z -- what such a kernel computes -- is inside C = 1 ... 8 at both
+    gains, on rows with one entry and with 600; the unrounded reference and the one that truncates Z are outside for
+    most pairs; and with nothing rounded the helper returns ``attention_bound`` itself."""
+    c, ref, bnd = _cases()[which]
+    ref16, b16 = E.attention_bf16(*_args(c), fused=False)
+    z16 = R.rne_bf16(c["z"]).astype(np.float32)
+    assert np.array_equal(z16.astype(np.float64), R.rne_bf16(c["z"]))              # (bf16 values are fp32 values)
+    got = E.attention_f32(c["sel"], z16, *_args(c)[2:])
+    r = _ratio(got, ref16, b16)
+    multi = c["sizes"] > 0
+    r_plain = _ratio({"post": ref["post"]}, ref16, b16)
+    trunc = E.attention(*_args(c), round_z=True, rounder=R.trunc_bf16)
+    r_trunc = _ratio({"post": trunc["post"]}, ref16, b16)
+    print(f"{which}: fp32 on bf16(Z) vs ref16, worst ratio {r.max():.3f}; unrounded reference {r_plain.max():.0f}, "
+          f"truncating reference {r_trunc.max():.0f}")
+    assert r.max() <= C_HOST and not b16["b_post_h"].any() and not ref16["d_post"].any()
+    assert (r_plain.max(axis=1) > C_HOST)[multi].mean() > 0.9 and (r_trunc.max(axis=1) > C_HOST)[multi].mean() > 0.9
+    same, b_same = E.attention_bf16(*_args(c), fused=False, round_z=False)
+    assert np.array_equal(same["post"], ref["post"]) and np.array_equal(b_same["b_post"], bnd["b_post"])
