@@ -1356,6 +1356,57 @@ int lpf_community_quality(int64_t n, int64_t nnz, const int32_t *row, const int3
                           const int32_t *comm, int64_t *inside, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Biased random walks (random_walk.hip; lpformer_amd/random_walks.py): the node2vec second-order walk by
+ * rejection sampling -- what an embedding baseline (Node2Vec, DeepWalk) is trained on.  The reference has no such code,
+ * and PyG's walkers live in CUDA extensions.  The symbol was added within ABI 16: the addition changes no existing
+ * symbol, so LPF_ABI_VERSION stays.
+ *
+ * Graph.  A CSR with sorted, unique int32 columns and a SYMMETRIC pattern, as in the two sections above (values ignored;
+ * a non-symmetric pattern is outside the contract).  A walk moves along stored entries; a stored self-loop is an entry
+ * like any other.  Row pointers outside [0, nnz] read as an empty row; a column outside [0, n) reads as a node without
+ * entries.
+ *
+ * Draws, those of the negatives section above with no new definition: key_w = key(seed, walk id),
+ * u(j) = mix64(key_w + G (j + 1)), node(u, d) = (u * d) >> 64.
+ *
+ * Walk w of the call has the id walk_base + w and the start starts[w] (int64).  walk[0] = start; a start outside
+ * [0, n) gives a row of -1 and a forced count of 0.  Step t = 1 .. L, with cur = walk[t - 1], d = the stored entries
+ * of row cur and T = max_tries:
+ *   1. d == 0: walk[t] = cur (the walk stays, as PyG pads).
+ *   2. Otherwise attempt a = 0, 1, ... draws the candidate x = col[rowptr[cur] + node(u(2 ((t - 1) T + a)), d)].
+ *   3. The FIRST candidate is taken without a test if t == 1, d == 1 or second_order == 0 (the caller passes 0 iff
+ *      p == q == 1).
+ *   4. Otherwise, with prev = walk[t - 2], x is of class RETURN (x == prev; weight 1 / p; this class wins over the
+ *      next), COMMON (x is stored in row prev; weight 1) or OUT (anything else; weight 1 / q),
+ *   5. and is accepted iff (u(2 ((t - 1) T + a) + 1) >> 1) < thr[class],
+ *   6. thr[class] = floor(2^63 weight / max weight), computed by the caller in exact arithmetic: the heaviest class
+ *      has 2^63 and always accepts.  Each threshold is at most 2^63.
+ *   7. After T refused attempts the last candidate is taken and forced[w] is incremented.
+ * A walk is a pure function of (seed, walk id, start, graph, L, thresholds, second_order, T): not of W, of how the
+ * caller cuts its walks into calls (walk_base), of the launch shape, of form or of timing; two runs are bitwise equal.
+ * Integers only; no floats on the device, no atomics; forced is per walk.
+ *
+ * walks int32 [L + 1][ldw] is STEP-MAJOR, walks[t * ldw + w] (a wavefront of form LANE stores one step as one
+ * contiguous line), ldw >= W; forced int32 [W] or NULL.  Limits (LPF_ERR_INVALID otherwise, before any launch):
+ * 0 <= n, nnz, W < 2^31 - 1, 1 <= L <= LPF_WALK_MAX_LENGTH, 1 <= max_tries <= LPF_WALK_MAX_TRIES, second_order 0 or
+ * 1, a known form, no NULL array but forced (col may be NULL when nnz == 0).  W == 0 or n == 0 returns LPF_OK without
+ * a launch (with n == 0 every start is outside the graph: the caller fills its -1).
+ * ---------------------------------------------------------------------------------------------- */
+#define LPF_WALK_MAX_LENGTH 65536
+#define LPF_WALK_MAX_TRIES 65536
+#define LPF_WALK_TRIES_DEFAULT 64
+/* form: LANE, one lane per walk, the bounds of rows cur and prev kept in registers; GROUP8, eight lanes per walk that
+ * probe row prev eight keys a round (a row of 600 entries: 3 rounds for 10).  Both give the same bits; DEFAULT is the
+ * one tools/random_walks_time.py measured faster. */
+#define LPF_WALK_FORM_LANE 0
+#define LPF_WALK_FORM_GROUP8 1
+#define LPF_WALK_FORM_DEFAULT 0
+int lpf_random_walks(int64_t n, int64_t nnz, const int64_t *rowptr, const int32_t *col, int64_t W,
+                     const int64_t *starts, int64_t walk_base, int32_t L, uint64_t seed, uint64_t thr_return,
+                     uint64_t thr_common, uint64_t thr_out, int32_t second_order, int32_t max_tries, int32_t form,
+                     int32_t *walks, int64_t ldw, int32_t *forced, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host side (liblpformer_host.so)
  * ---------------------------------------------------------------------------------------------- */
 

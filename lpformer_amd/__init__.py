@@ -45,6 +45,11 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
     bootstrap_metrics, compare_metrics  standard errors, percentile intervals and paired p-values of Hits@K / MRR / AUC by
                                         a bootstrap over the positives (device resampling kernel); bootstrap_by_bin,
                                         bootstrap_sums (the building block), bootstrap_sums_reference (numpy restatement)
+    random_walks, node2vec_embeddings   node2vec's biased second-order walks drawn on the device (rejection sampling with
+                                        exact integer thresholds: a pure function of seed and walk id): Walks (walks,
+                                        forced), walk_thresholds, walk_pairs (skip-gram pairs as PyG cuts them), and the
+                                        Node2Vec embeddings trained on them (skip-gram in torch); the numpy restatement
+                                        is random_walks.walks_reference
     link_split                          edge list + features -> a data dict with train / valid / test positives and
                                         edge-aware negatives, ready for fit and evaluate_model
     graph, data                         CSR containers and the data-dict builder
@@ -69,6 +74,7 @@ from .graphed import GraphedScorer, PlannedScorer  # noqa: F401
 from .link_transformer import MLP, LinkTransformer, mlp_score  # noqa: F401
 from .ppr import calc_ppr, calc_ppr_gpu, get_ppr, load_or_calc_ppr, ppr_coo  # noqa: F401
 from .pyg_api import LPFormer  # noqa: F401
+from .random_walks import Walks, node2vec_embeddings, random_walks, walk_pairs, walk_thresholds  # noqa: F401
 from .recommend import Recommendations, recommend  # noqa: F401
 from .similar import Similar, similar_nodes, similar_reference  # noqa: F401
 from .structure import (CORE_BINS, DEGREE_BINS, NodeStructure, node_structure, pair_node_values,  # noqa: F401
@@ -86,4 +92,5 @@ __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_
            "ball_jaccard", "bootstrap_sums", "bootstrap_sums_reference", "bootstrap_metrics", "compare_metrics",
            "bootstrap_by_bin", "similar_nodes", "similar_reference", "Similar", "node_structure", "NodeStructure",
            "structure_reference", "pair_node_values", "same_component", "DEGREE_BINS", "CORE_BINS", "communities",
-           "Communities", "communities_reference", "partition_quality", "same_community", "COMMUNITY_BINS"]
+           "Communities", "communities_reference", "partition_quality", "same_community", "COMMUNITY_BINS", "random_walks",
+           "node2vec_embeddings", "walk_pairs", "walk_thresholds", "Walks"]
