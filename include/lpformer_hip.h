@@ -1407,6 +1407,68 @@ int lpf_random_walks(int64_t n, int64_t nnz, const int64_t *rowptr, const int32_
                      int32_t *walks, int64_t ldw, int32_t *forced, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Node2Vec's skip-gram update with negative sampling (skipgram.hip; lpformer_amd/skipgram.py): one
+ * synchronous optimiser step on an embedding table, every gradient taken at the table as it stands when the step
+ * begins.  The loss is PyG's Node2Vec.loss, the update torch.optim.SparseAdam; only the evaluation is new: no
+ * [windows, context, dim] block, no float atomics, one fixed summation order, repeatable bits.  The reference has no
+ * such code.  The three symbols were added within ABI 16: the addition changes no existing symbol, so LPF_ABI_VERSION
+ * stays.
+ *
+ * Walk buffers.  pos and neg are STEP-MAJOR int32 [L + 1][ld], as lpf_random_walks writes them, holding Wp and Wn
+ * walks; neither is unfolded in memory.  A walk has nwin = L + 2 - context windows; window (w, o) gives the pairs
+ * (c, x) = (walk[o][w], walk[o + k][w]), k = 1 .. context - 1; pair id = (w nwin + o)(context - 1) + (k - 1), the
+ * negative buffer's ids following the positive buffer's.  M = Mp + Mn, Mp = Wp nwin (context - 1), Mn likewise.
+ * logit l = <E[c], E[x]>; with s = 1 / (1 + exp(-l)) a positive pair adds -log(s + 1e-15) / Mp to the loss and a
+ * negative pair -log((1 - s) + 1e-15) / Mn.  A pair that holds an id outside [0, n) has coefficient 0 and loss 0 (it
+ * still counts in Mp or Mn) and is written with both ids -1.  A pair with c == x is an ordinary pair.
+ *
+ * Tables are float [rows][ld] with ld >= dim, ld % 4 == 0 and a 16-byte aligned base; dim % 4 == 0,
+ * 4 <= dim <= LPF_SKIPGRAM_MAX_DIM.  Every entry returns LPF_ERR_INVALID before any launch for arguments outside its
+ * limits, and LPF_OK without a launch for an empty call.  No id read from a buffer indexes anything before it is
+ * range-checked.
+ * ---------------------------------------------------------------------------------------------- */
+#define LPF_SKIPGRAM_MAX_DIM 512
+/* occurrences per chunk of lpf_skipgram_grad_rows_f32: part of its result's definition */
+#define LPF_SKIPGRAM_CHUNK 128
+/* windows per workgroup of lpf_skipgram_coef_f32: partial holds ceil((Wp + Wn) nwin / this) sums */
+#define LPF_SKIPGRAM_BLOCK_WINDOWS 16
+/* coef float [M]: g = dloss/dl per pair, 1 / Mp or 1 / Mn folded in -- the logit in fp32 (one order per dim), the
+ * sigmoid and the quotient in fp64 from it, rounded once.  centre, other int32 [M]: the pair's ids (-1, -1 and g = 0
+ * for a bad pair).  partial double [partial_len >= ceil((Wp + Wn) nwin / LPF_SKIPGRAM_BLOCK_WINDOWS)]: the
+ * workgroups' loss sums; *loss (one double) is their sum in one fixed order.  A group of 16 lanes per window loads the
+ * centre row once and walks its context - 1 partners; rows are read as 16-byte loads.
+ * Limits: 0 <= n < 2^31 - 1, 1 <= L <= LPF_WALK_MAX_LENGTH, 2 <= context <= L + 1, 0 <= Wp <= ldp, 0 <= Wn <= ldn,
+ * M < 2^31 - 1.  Wp + Wn == 0: LPF_OK, nothing written (*loss included). */
+int lpf_skipgram_coef_f32(int64_t n, int32_t dim, const float *table, int64_t ldt, int32_t L, int32_t context,
+                          const int32_t *pos, int64_t Wp, int64_t ldp, const int32_t *neg, int64_t Wn, int64_t ldn,
+                          float *coef, int32_t *centre, int32_t *other, double *partial, int64_t partial_len,
+                          double *loss, void *stream);
+/* grad float [U][ldg]: grad[u] = sum over the occurrences e in [seg[u], seg[u + 1]) of coef[occ_pair[e]] *
+ * E[occ_other[e]], one fused multiply-add per element and occurrence, IN THE LISTED ORDER within a chunk: the segment
+ * is cut at seg[u] + j LPF_SKIPGRAM_CHUNK, each chunk is summed from zero by one wavefront, and the chunks' rows are
+ * added in chunk order.  The result is a function of the inputs and of that constant only -- not of groups (the
+ * number of workgroups; 0: one wavefront per LPF_SKIPGRAM_CHUNK occurrences of the list), of the launch shape or of
+ * timing.  The caller lists, for pair i, the occurrences (row c_i, other x_i, pair i) and (row x_i, other c_i,
+ * pair i), sorted by row and within a row by occurrence id; seg int64 [U + 1] ascending from 0 to n_occ.  An
+ * occurrence whose other is outside [0, n) or whose pair is outside [0, M) adds nothing; segment offsets are clamped
+ * to [0, n_occ].  scratch float [scratch_rows >= ceil(n_occ / LPF_SKIPGRAM_CHUNK)][ldg], 16-byte aligned: the later
+ * chunks' rows.  Reads the table, writes grad and scratch only.  U == 0: LPF_OK without a launch. */
+int lpf_skipgram_grad_rows_f32(int64_t n, int32_t dim, const float *table, int64_t ldt, int64_t M, const float *coef,
+                               int64_t n_occ, const int32_t *occ_other, const int32_t *occ_pair, int64_t U,
+                               const int64_t *seg, float *grad, int64_t ldg, float *scratch, int64_t scratch_rows,
+                               int32_t groups, void *stream);
+/* torch.optim.SparseAdam on the U DISTINCT rows rows[u] of table, exp_avg and exp_avg_sq ([n][ldt], [n][lds],
+ * [n][lds]), in place, from grad [U][ldg]:  m += (g - m)(1 - beta1);  v += (g g - v)(1 - beta2);
+ * param -= lr sqrt(bias2) / bias1 * m / (sqrt(v) + eps).  step >= 1 is the global step count of this update, and the
+ * caller passes bias1 = 1 - beta1^step and bias2 = 1 - beta2^step computed in double (both in (0, 1]).  A listed row
+ * outside [0, n) is skipped; rows not listed are untouched.  0 <= beta < 1, lr, eps >= 0; 1 - beta1, 1 - beta2, eps
+ * and the step size are rounded to fp32 once, the arithmetic is fp32.  U == 0 or n == 0: LPF_OK without a launch. */
+int lpf_sparse_adam_rows_f32(int64_t n, int32_t dim, float *table, int64_t ldt, float *exp_avg, float *exp_avg_sq,
+                             int64_t lds, int64_t U, const int32_t *rows, const float *grad, int64_t ldg, double lr,
+                             double beta1, double beta2, double eps, int64_t step, double bias1, double bias2,
+                             void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host side (liblpformer_host.so)
  * ---------------------------------------------------------------------------------------------- */
 

@@ -50,6 +50,10 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
                                         forced), walk_thresholds, walk_pairs (skip-gram pairs as PyG cuts them), and the
                                         Node2Vec embeddings trained on them (skip-gram in torch); the numpy restatement
                                         is random_walks.walks_reference
+    skipgram_step, skipgram_state       one Node2Vec skip-gram step with negative sampling on the device (PyG's loss,
+                                        SparseAdam; three kernels, one summation order, repeatable bits): what
+                                        node2vec_embeddings(trainer="device") runs; SkipGramState, skipgram_reference
+                                        (the fp64 restatement on the CPU)
     link_split                          edge list + features -> a data dict with train / valid / test positives and
                                         edge-aware negatives, ready for fit and evaluate_model
     graph, data                         CSR containers and the data-dict builder
@@ -75,6 +79,7 @@ from .link_transformer import MLP, LinkTransformer, mlp_score  # noqa: F401
 from .ppr import calc_ppr, calc_ppr_gpu, get_ppr, load_or_calc_ppr, ppr_coo  # noqa: F401
 from .pyg_api import LPFormer  # noqa: F401
 from .random_walks import Walks, node2vec_embeddings, random_walks, walk_pairs, walk_thresholds  # noqa: F401
+from .skipgram import SkipGramState, skipgram_reference, skipgram_state, skipgram_step  # noqa: F401
 from .recommend import Recommendations, recommend  # noqa: F401
 from .similar import Similar, similar_nodes, similar_reference  # noqa: F401
 from .structure import (CORE_BINS, DEGREE_BINS, NodeStructure, node_structure, pair_node_values,  # noqa: F401
@@ -93,4 +98,5 @@ __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_
            "bootstrap_by_bin", "similar_nodes", "similar_reference", "Similar", "node_structure", "NodeStructure",
            "structure_reference", "pair_node_values", "same_component", "DEGREE_BINS", "CORE_BINS", "communities",
            "Communities", "communities_reference", "partition_quality", "same_community", "COMMUNITY_BINS", "random_walks",
-           "node2vec_embeddings", "walk_pairs", "walk_thresholds", "Walks"]
+           "node2vec_embeddings", "walk_pairs", "walk_thresholds", "Walks", "SkipGramState", "skipgram_state",
+           "skipgram_step", "skipgram_reference"]

@@ -9,7 +9,8 @@ concatenated to ``x`` on the OGB link leaderboards.  PyG's ``Node2Vec`` takes it
     walks_reference(csr, starts, ...)                                  the numpy restatement, what a host CSR without a GPU runs
     walk_thresholds(p, q)                                              the three integer acceptance thresholds
     walk_pairs(walks, context)                                         int64 [2, M] (centre, context) pairs, as PyG cuts them
-    node2vec_embeddings(source, dim, ...)                              (emb float32 [n, dim], losses): skip-gram in torch
+    node2vec_embeddings(source, dim, ...)                              (emb float32 [n, dim], losses): skip-gram in torch,
+                                                                       or on the device with trainer="device" (skipgram.py)
 
 Contract (shared by the kernel, ``lpf_random_walks`` in csrc/random_walk.hip, and ``walks_reference``, which are equal
 integer for integer).  The graph is a CSR with sorted, unique int32 columns and a SYMMETRIC pattern, the typing
@@ -49,7 +50,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib, graph, negatives, ops, sources
+from . import _lib, graph, negatives, ops, skipgram, sources
 from ._lib import check, ptr
 
 MAX_LENGTH = _lib.CONST["LPF_WALK_MAX_LENGTH"]
@@ -240,7 +241,8 @@ def _skipgram_loss(emb: torch.nn.Embedding, pos: torch.Tensor, neg: torch.Tensor
 
 def node2vec_embeddings(source, dim: int = 128, *, walk_length: int = 20, context: int = 10, walks_per_node: int = 10,
                         p=1.0, q=1.0, num_neg: int = 1, epochs: int = 1, batch_walks: int = 1280, lr: float = 0.01,
-                        seed: int = 0, test_set: bool = False, max_tries=TRIES):
+                        seed: int = 0, test_set: bool = False, max_tries=TRIES, trainer: str = "torch",
+                        max_steps=None):
     """Node2Vec embeddings of the typing adjacency: ``(emb float32 [n, dim] on the device, losses)``, ``losses`` the mean
     loss of each epoch's steps.
 
@@ -255,6 +257,17 @@ def node2vec_embeddings(source, dim: int = 128, *, walk_length: int = 20, contex
     The WALKS are a pure function of their arguments; the embeddings are NOT bitwise repeatable, because torch's sparse
     gradient accumulation adds in no fixed order.  The shuffle, the initial table (standard normal, as
     ``nn.Embedding``) and the negatives come from one ``torch.Generator`` seeded with ``seed``.
+
+    ``trainer="device"`` runs the same step -- the same loss, the same ``SparseAdam`` -- through
+    ``skipgram.skipgram_step``: no gathered blocks, no float atomics, one summation order.  It needs a
+    GPU source and ``dim % 4 == 0 and dim <= 512`` (``ValueError`` otherwise), takes the walks straight from the
+    kernel's step-major buffer, and draws the table, the shuffle and the noise nodes from the same generator in the
+    same order, so both trainers see the same walks and negatives.  With ``trainer="device"`` the embeddings ARE
+    bitwise repeatable on one machine: two calls with equal arguments give equal bits.  The default stays ``"torch"``.
+    The two trainers differ in VALUE where torch's fp32 ``1 - sigmoid(l)`` is exactly 0 (l above about 17: loss 34.5,
+    gradient 0); the device evaluates the same expression in fp64 from its fp32 logit.
+    ``max_steps``: stop after this many optimiser steps in all (None: whole epochs); ``losses`` then holds the mean
+    over the steps taken of every epoch begun.
 
     Leakage: compute the embeddings on the TRAINING graph -- ``test_set=False`` for a model source, or the adjacency of
     ``link_split``'s ``data["adj_mask"]`` -- never on an edge list that still holds validation or test edges.  Use them
@@ -271,7 +284,15 @@ def node2vec_embeddings(source, dim: int = 128, *, walk_length: int = 20, contex
     chunk = negatives._check_count(batch_walks, "batch_walks", 1, _MAX)
     seed = negatives._check_seed(seed)
     walk_thresholds(p, q)
+    if trainer not in ("torch", "device"):
+        raise ValueError(f'trainer must be "torch" or "device"; got {trainer!r}')
+    if max_steps is not None:
+        max_steps = negatives._check_count(max_steps, "max_steps", 1, 1 << 62)
+    if trainer == "device" and (dim % 4 or dim > skipgram.MAX_DIM):
+        raise ValueError(f'trainer="device" needs dim % 4 == 0 and dim <= {skipgram.MAX_DIM}; got {dim}')
     dev, adj, _, _ = sources.resolve(source, test_set, torch.empty(0), who="node2vec_embeddings", host_ok=True)
+    if trainer == "device" and dev is None:
+        raise ValueError('trainer="device" needs a source on a GPU; a host graph.CSR without one trains with "torch"')
     where = torch.device("cpu") if dev is None else dev
     n = int(adj.n)
     if n <= 0:
@@ -279,12 +300,15 @@ def node2vec_embeddings(source, dim: int = 128, *, walk_length: int = 20, contex
     gen = torch.Generator(device=where)
     gen.manual_seed(seed & ((1 << 63) - 1))
     table = torch.randn((n, dim), generator=gen, device=where, dtype=torch.float32)
+    if trainer == "device":
+        return _train_on_device(table, adj, gen, L=L, context=context, r=r, num_neg=num_neg, epochs=epochs,
+                                chunk=chunk, lr=lr, p=p, q=q, seed=seed, max_tries=max_tries, max_steps=max_steps)
     emb = torch.nn.Embedding(n, dim, sparse=True, _weight=table)
     opt = torch.optim.SparseAdam(list(emb.parameters()), lr=lr)
     # a host source without a GPU walks through the restatement; with one, `adj` is the resident device copy
     walk_source = source if dev is None else adj
     per_epoch = n * r
-    losses = []
+    losses, done = [], 0
     for epoch in range(epochs):
         order = torch.randperm(n, generator=gen, device=where).repeat(r)
         total = torch.zeros((), dtype=torch.float32, device=where)
@@ -302,5 +326,41 @@ def node2vec_embeddings(source, dim: int = 128, *, walk_length: int = 20, contex
             opt.step()
             total += loss.detach()
             steps += 1
+            done += 1
+            if done == max_steps:
+                break
         losses.append(float(total) / steps)
+        if done == max_steps:
+            break
     return emb.weight.detach(), losses
+
+
+def _train_on_device(table, adj, gen, *, L, context, r, num_neg, epochs, chunk, lr, p, q, seed, max_tries, max_steps):
+    """``node2vec_embeddings``' loop with ``skipgram.skipgram_step`` as the step: the same draws from ``gen`` in the
+    same order as the torch trainer.  The walks are handed over as the kernel's step-major buffer (the base of the
+    transposed view, no copy); the negative walks are written step-major as well: the starts, then the noise."""
+    dev, n = table.device, int(adj.n)
+    state = skipgram.skipgram_state(table)
+    per_epoch = n * r
+    losses, done = [], 0
+    for epoch in range(epochs):
+        order = torch.randperm(n, generator=gen, device=dev).repeat(r)
+        total = torch.zeros((), dtype=torch.float64, device=dev)
+        steps = 0
+        for lo, m in sources.chunks(per_epoch, chunk):
+            start = order[lo:lo + m]
+            walks = random_walks(adj, start, length=L, p=p, q=q, seed=seed, max_tries=max_tries,
+                                 walk_base=epoch * per_epoch + lo).walks
+            noise = torch.randint(n, (m * num_neg, L), generator=gen, device=dev)
+            neg = torch.empty((L + 1, m * num_neg), dtype=torch.int32, device=dev)
+            neg[0] = start.repeat(num_neg)
+            neg[1:] = noise.t()
+            total += skipgram.skipgram_step(table, state, walks.t(), neg, context, lr=lr)
+            steps += 1
+            done += 1
+            if done == max_steps:
+                break
+        losses.append(float(total) / steps)                        # the one read per epoch
+        if done == max_steps:
+            break
+    return table, losses
