@@ -1469,6 +1469,51 @@ int lpf_sparse_adam_rows_f32(int64_t n, int32_t dim, float *table, int64_t ldt, 
                              void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Common-neighbour pooling (cn_pool.hip; lpformer_amd/ncn.py): the sum of a table's rows over the common
+ * neighbours of a pair -- what NCN (Wang, Yang, Zhang: Neural Common Neighbor with Completion for Link Prediction)
+ * scores a pair from, and LPFormer's pairwise stage with uniform attention on the common neighbours only.  The
+ * reference counts common neighbours with dense adj[edge].to_dense() rows ([BS, N] per batch, src/train/eval.py:21-41)
+ * and has no such pooling.  Both symbols were added within ABI 16: the addition changes no existing symbol, so
+ * LPF_ABI_VERSION stays.
+ *
+ * Graph: the CSR lpf_pair_heuristics_f32 reads -- sorted, unique int32 columns, a binary pattern.  For pair
+ * p = (a, b) = (pairs[p], pairs[pairs_ld + p]):  C(p) = N(a) & N(b) in ascending node id, u_1 < ... < u_k.  A pair with
+ * an id outside [0, n) has k = 0; a == b gives C = N(a) (what lpf_pair_heuristics_f32 counts); a node is in its own
+ * neighbourhood only where the graph stores a self-loop, so a positive pair's own edge never enters its pool.
+ *   pool[p] = sum_j ( sum_{i in chunk j} w[u_i] T[u_i] ),  chunk j = the entries [j C, (j + 1) C) of C(p),
+ * C = LPF_CN_POOL_CHUNK: each chunk is summed from zero in ascending order, one fp32 fused multiply-add per element
+ * and entry, and the chunks' rows are added in chunk order to a total that starts at zero.  The result is a function
+ * of ({a, b}, graph, T, w) and of that constant only -- not of the pair's position, of (a, b) versus (b, a), of
+ * split_threshold, of the launch shape or of timing; no float atomics.  The pair walks its shorter row and
+ * binary-searches the other; walked rows of at most split_threshold entries (negative: LPF_HEUR_SPLIT_DEFAULT) are
+ * flattened 64 probes per wavefront, longer ones get a 256-thread workgroup each, and the two classes agree bitwise.
+ *
+ * Tables are float [rows][ld] with ld >= dim, ld % 4 == 0 and a 16-byte aligned base; dim % 4 == 0,
+ * 4 <= dim <= LPF_CN_POOL_MAX_DIM.  0 < P < 2^31 - 1, 0 < n <= INT32_MAX.  Every entry returns LPF_ERR_INVALID before
+ * any launch for arguments outside its limits, and LPF_OK without a launch for P == 0.  No id read from memory indexes
+ * anything before it is range-checked: a common column outside [0, n) (a malformed graph) counts in cn, is listed by
+ * lpf_cn_entries as it stands and takes its place in its chunk, but adds nothing to the pool.
+ * ---------------------------------------------------------------------------------------------- */
+#define LPF_CN_POOL_MAX_DIM 512
+/* common neighbours per chunk of lpf_cn_pool_f32: part of its result's definition */
+#define LPF_CN_POOL_CHUNK 64
+/* pool float [P][ldp]: every row is written, zeros where k = 0; what lies behind dim in a row is left alone.  w float
+ * [n] or NULL (1.0).  table float [n][ldt].  cn int32 [P] or NULL: k.  scratch int32 [P + 1] (the long-pair list).
+ * The intersection and the row gather are one pass: no list of entries exists in memory. */
+int lpf_cn_pool_f32(int64_t P, int64_t n, const int64_t *pairs, int64_t pairs_ld, const int64_t *rowptr,
+                    const int32_t *col, const float *w, int32_t dim, const float *table, int64_t ldt,
+                    int32_t split_threshold, int32_t *scratch, float *pool, int64_t ldp, int32_t *cn, void *stream);
+/* C(p) itself: node[seg[p] + i] = u_(i + 1).  seg int64 [P + 1]: the exclusive scan of cn (the caller's), n_ent the
+ * length of node, 0 <= n_ent < 2^31 - 1.  Pair p writes its first seg[p + 1] - seg[p] entries and nothing else: the
+ * segment offsets are clamped to [0, n_ent] (and seg[p + 1] to seg[p] from below), as lpf_skipgram_grad_rows_f32
+ * clamps its own, so a seg that disagrees with the graph writes inside its own segments only and never outside
+ * node[0 .. n_ent); where a segment is longer than C(p), its tail is left as it was.  n_ent == 0: LPF_OK without a
+ * launch.  scratch int32 [P + 1]. */
+int lpf_cn_entries(int64_t P, int64_t n, const int64_t *pairs, int64_t pairs_ld, const int64_t *rowptr,
+                   const int32_t *col, int32_t split_threshold, int32_t *scratch, const int64_t *seg, int64_t n_ent,
+                   int32_t *node, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host side (liblpformer_host.so)
  * ---------------------------------------------------------------------------------------------- */
 

@@ -54,6 +54,11 @@ Public surface mirrors the reference (HarryShomer/LPFormer):
                                         SparseAdam; three kernels, one summation order, repeatable bits): what
                                         node2vec_embeddings(trainer="device") runs; SkipGramState, skipgram_reference
                                         (the fp64 restatement on the CPU)
+    cn_pool, NCNPredictor               the sum of a table's rows over each pair's common neighbours (device fused
+                                        intersect-and-gather kernel, one summation order, differentiable in the table)
+                                        and NCN's predictor on it -- LPFormer with uniform attention on the common
+                                        neighbours only; cn_entries (the common neighbours themselves), ncn_scores,
+                                        cn_pool_reference / cn_entries_reference (the fp64 / numpy restatements)
     link_split                          edge list + features -> a data dict with train / valid / test positives and
                                         edge-aware negatives, ready for fit and evaluate_model
     graph, data                         CSR containers and the data-dict builder
@@ -73,6 +78,8 @@ from .hard_negatives import HardNegatives, heart_negatives, twohop_rows  # noqa:
 from .heuristics import pair_heuristics  # noqa: F401
 from .hops import ball_jaccard, elph_features, hop_counts_reference, pair_hop_counts  # noqa: F401
 from .katz import katz_from_walks, pair_katz, pair_walks, walks_reference  # noqa: F401
+from .ncn import (CnEntries, NCNPredictor, cn_entries, cn_entries_reference, cn_pool,  # noqa: F401
+                  cn_pool_reference, ncn_scores)
 from .negatives import UniformNegatives, negative_pairs, negative_rows, negatives_reference  # noqa: F401
 from .graphed import GraphedScorer, PlannedScorer  # noqa: F401
 from .link_transformer import MLP, LinkTransformer, mlp_score  # noqa: F401
@@ -99,4 +106,5 @@ __all__ = ["LinkTransformer", "mlp_score", "MLP", "LPFormer", "calc_ppr", "calc_
            "structure_reference", "pair_node_values", "same_component", "DEGREE_BINS", "CORE_BINS", "communities",
            "Communities", "communities_reference", "partition_quality", "same_community", "COMMUNITY_BINS", "random_walks",
            "node2vec_embeddings", "walk_pairs", "walk_thresholds", "Walks", "SkipGramState", "skipgram_state",
-           "skipgram_step", "skipgram_reference"]
+           "skipgram_step", "skipgram_reference", "cn_pool", "cn_entries", "cn_pool_reference", "cn_entries_reference",
+           "CnEntries", "NCNPredictor", "ncn_scores"]
